@@ -12,6 +12,11 @@ Launch (driver contract):
   python bench.py --gpus 1 --steps K --warmup W                 # single rank
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+--dump-outputs DIR also writes the last timed step's outputs as .npy files
+(inputs are seeded, so two builds can be compared output for output);
+--full is where measurements that need runs of their own belong.
 """
 import argparse
 import json
@@ -45,6 +50,15 @@ def main():
                     choices=["data_parallel", "voting_parallel"],
                     help="histogram sync strategy (voting reduces only the "
                          "globally-voted top-K features per split)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extended measurements that take runs "
+                         "of their own; a plain run only sets up, warms up, "
+                         "times the steps and prints the result line (there "
+                         "are none today — ablations are selected by their "
+                         "own options)")
     args = ap.parse_args()
 
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -55,6 +69,9 @@ def main():
     comm = init_from_env()
     rank = comm.rank
     world = comm.world_size
+    # seed every generator, CPU and GPU, so that the same arguments give the
+    # same inputs from run to run (the GPU draws below keep their seed)
+    torch.manual_seed(1234 + rank)
     use_gpu = torch.cuda.is_available()
     device = torch.device("cuda") if use_gpu else torch.device("cpu")
     if use_gpu and world > 1:
@@ -119,6 +136,40 @@ def main():
                        nf, cat_idx)
 
 
+# --dump-outputs budget: 64 MB in all; the row scores get the lion's share,
+# one tree's node arrays are a few KB
+DUMP_MAX_SCORE_ELEMS = 12_000_000   # float32 -> 48 MB
+
+
+def sample_rows(n_rows, n_cols):
+    """Row ids to dump when n_rows x n_cols scores exceed the budget, else
+    None.  Fixed and seeded; drawn with replacement (cheap at any n)."""
+    import numpy as np
+    if n_rows * n_cols <= DUMP_MAX_SCORE_ELEMS:
+        return None
+    m = DUMP_MAX_SCORE_ELEMS // n_cols
+    return np.random.default_rng(20240607).integers(0, n_rows, m)
+
+
+def dump_outputs(session, out_dir):
+    """Write what the last timed step handed back — the updated raw scores of
+    this rank's rows and the tree it grew per output — as <name>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    preds = session.preds
+    idx = sample_rows(preds.shape[0], preds.shape[1])
+    if idx is not None:
+        preds = preds[torch.from_numpy(idx).to(preds.device)]
+    np.save(os.path.join(out_dir, "raw_scores.npy"),
+            preds.detach().float().cpu().numpy())
+    K = session.K
+    for k, tree in enumerate(session.trees[-K:]):
+        for field in ("feature", "threshold", "thr_bin", "left", "right",
+                      "value", "count", "gain"):
+            np.save(os.path.join(out_dir, f"last_tree{k}_{field}.npy"),
+                    np.asarray(getattr(tree, field), dtype=np.float64))
+
+
 def run_session(args, comm, rank, world, use_gpu, device, X, y, n, nf,
                 cat_idx):
     from mmlspark_amd.models.gbdt.objectives import make_objective
@@ -151,6 +202,9 @@ def run_session(args, comm, rank, world, use_gpu, device, X, y, n, nf,
         t = t.to(device) if use_gpu else t
         comm.all_reduce(t, op="max")
     elapsed = float(t[0])
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(session, args.dump_outputs)
 
     if rank == 0:
         total_rows = n * world * args.steps

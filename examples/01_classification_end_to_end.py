@@ -3,6 +3,7 @@ evaluate, explain, and save — the core MMLSpark workflow
 (adult-census-shaped synthetic data; runs on CPU or MI355X)."""
 import os
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -42,5 +43,7 @@ shap = TabularSHAP(inputCols=cols, model=LightGBMClassifier(
     backgroundData=df.head(200))
 print(shap.transform(df.head(2))["explanation"].iloc[0])
 
-model.save("/tmp/census_model")
-print("saved to /tmp/census_model")
+# a fresh directory: a fixed path may belong to another user on a shared box
+out_dir = os.path.join(tempfile.mkdtemp(), "census_model")
+model.save(out_dir)
+print("saved to", out_dir)

@@ -10,6 +10,7 @@ The fitted model is identical on every rank, bit for bit — rank 0 persists
 it (docs/distributed.md, docs/migration.md)."""
 import os
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -43,6 +44,7 @@ print(f"[rank {rank}/{world}] local holdout acc {acc:.3f}, "
       f"{model.booster.num_trees} trees")
 
 if rank == 0:
-    model.save("/tmp/distributed_gbdt_model")
-    print("rank 0 saved /tmp/distributed_gbdt_model "
-          "(identical on every rank)")
+    # a fresh directory: a fixed path may belong to another user on a shared box
+    out_dir = os.path.join(tempfile.mkdtemp(), "distributed_gbdt_model")
+    model.save(out_dir)
+    print("rank 0 saved", out_dir, "(identical on every rank)")
