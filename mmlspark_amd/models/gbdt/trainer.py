@@ -419,12 +419,16 @@ class TreeGrower:
             lf = _Leaf(int(nid), d["leaf_rows"][offs[i]:offs[i + 1]], None,
                        0, 0, 0, 0)
             leaves.append(lf)
+        # concatenated leaf rows as the native prediction update takes them
+        self.native_leaves = (d["leaf_rows"], d["leaf_offsets"], nodes)
         return tree, leaves
 
     native_ok = True  # sparse grower overrides (no arena path yet)
+    native_leaves = None  # set by the native grower for the tree just grown
 
     def grow(self, rows_root: torch.Tensor, grad: torch.Tensor,
              hess: torch.Tensor, feat_mask) -> (Tree, List):
+        self.native_leaves = None
         if (self.native_ok and self.fixed and not self.voting
                 and not os.environ.get(
                     "MMLSPARK_AMD_NO_NATIVE_GROWER")):
@@ -871,7 +875,18 @@ class TrainingSession:
                 # one fused update: concat leaf row lists + repeat leaf values
                 t0 = time.perf_counter()
                 live = [lf for lf in leaves if lf.rows.numel()]
-                if live:
+                native = self.grower.native_leaves
+                if (native is not None and not dropped
+                        and preds.is_cuda and preds.dtype == torch.float32):
+                    from ...ops import _hip_grower
+                    leaf_rows, leaf_offsets, nodes = native
+                    vals = torch.tensor(
+                        [float(tree.value[nid]) * tree.shrinkage
+                         for nid in nodes], dtype=torch.float32,
+                        device=device)
+                    _hip_grower.apply_leaf_values(preds[:, k], leaf_rows,
+                                                  leaf_offsets, vals)
+                elif live:
                     all_rows = torch.cat([lf.rows for lf in live]).long()
                     sizes = [lf.rows.numel() for lf in live]
                     vals = torch.tensor(

@@ -15,8 +15,8 @@
 //
 //  * SPECULATION: a popped leaf's split work is independent of processing
 //    order (its split was fixed at creation), so the driver pre-launches the
-//    next-best candidate's whole chain (partition → smaller-child hist →
-//    sibling subtraction → scan → pinned readback behind a HIP event) while
+//    next-best candidate's whole chain (count → scatter → smaller-child hist
+//    → sibling subtract+scan → pinned readback behind a HIP event) while
 //    the host waits on the current readback.  Commit order stays exactly
 //    leaf-wise.  The chain never blocks the host: child ranges resolve from
 //    the DEVICE-side left count, which rides back with the scan result.
@@ -44,14 +44,17 @@ void launch_arena_gather(const void*, long, const float*, const float*,
                          const int*, long, int, double, double, void*, void*,
                          int*, hipStream_t);
 void launch_partition_arena(const void*, const void*, const int*, void*,
-                            void*, int*, int*, long, int, long, long, int,
-                            int, const unsigned*, int*, int*, hipStream_t);
+                            void*, int*, long, int, long, long, int, int,
+                            const unsigned*, int*, int*, long, int,
+                            hipStream_t);
 void launch_hist_pair_range(const void*, const void*, long, long, long,
                             long long*, int, int, int, const int*, int,
                             hipStream_t);
-void launch_split_scan_fixed(const long long*, int, long, int, float, float,
-                             float, float, float, long, const bool*, float*,
-                             float*, double, double, hipStream_t);
+void launch_sibling_scan(const long long*, const long long*, long long*, int,
+                         long, int, float, float, float, float, long,
+                         const bool*, float*, double, double, hipStream_t);
+void launch_apply_leaf_values(float*, long, const int*, const long*, int,
+                              const float*, long, hipStream_t);
 }
 
 static hipStream_t grower_stream() {
@@ -89,12 +92,15 @@ struct GrowCtx {
   torch::Tensor cat_idx_dev;  // i64 device indices for index_select
   torch::Tensor scratch;    // partition block counters (stream-ordered reuse)
   torch::Tensor total;      // partition left-count (stream-ordered reuse)
-  torch::Tensor dst_idx;    // (n_arena,) i32 per-split dest ranks (reused)
+  // per-tree histogram slabs, one slot per split: small children accumulate
+  // into pre-zeroed slots, big children are written whole by the sibling scan
+  torch::Tensor slab_zero, slab_raw;
+  long slab_used_zero = 0, slab_used_raw = 0;
 };
 
 struct SplitJob {
   torch::Tensor hist_l, hist_r;
-  torch::Tensor scan_host;  // (2,6) f32 pinned
+  torch::Tensor scan_host;  // (nh, nf_pad, 6) f32 pinned per-feature records
   torch::Tensor nl_host;    // (1,) i32 pinned — local left count readback
   torch::Tensor cat_host;   // (nh, ncat, nb, 3) i64 pinned — cat hist rows
   torch::Tensor bits_host;  // (8,) i32 pinned — partition bitset staging
@@ -131,12 +137,22 @@ struct CandCmp {
   }
 };
 
+// a histogram slot from the per-tree slab; per-split allocation once
+// speculation has used the slab up
+torch::Tensor hist_slot(GrowCtx& ctx, bool zeroed) {
+  torch::Tensor& slab = zeroed ? ctx.slab_zero : ctx.slab_raw;
+  long& used = zeroed ? ctx.slab_used_zero : ctx.slab_used_raw;
+  if (used < slab.size(0)) return slab.select(0, used++);
+  auto opt = ctx.pair[0].options();
+  return zeroed ? torch::zeros({ctx.npairs * 8, ctx.n_bins, 3}, opt)
+                : torch::empty({ctx.npairs * 8, ctx.n_bins, 3}, opt);
+}
+
 // histogram over an arena segment [lo+?, ...) of buffer `buf`; side >= 0
 // resolves the child sub-range from the device left count (no host sync)
 torch::Tensor build_hist(GrowCtx& ctx, int buf, long lo, long m,
                          const int* nl_dev = nullptr, int side = -1) {
-  auto hist = torch::zeros({ctx.npairs * 8, ctx.n_bins, 3},
-                           ctx.pair[buf].options());
+  auto hist = hist_slot(ctx, true);
   launch_hist_pair_range(
       ctx.pair[buf].data_ptr(), ctx.ghq[buf].data_ptr(), ctx.n_arena, lo, m,
       (long long*)hist.data_ptr<int64_t>(), ctx.n_bins, ctx.npairs,
@@ -148,43 +164,52 @@ torch::Tensor build_hist(GrowCtx& ctx, int buf, long lo, long m,
   return hist;
 }
 
-// launch the (2, nf_pad) scan of stacked child histograms; result lands in a
-// pinned host buffer behind an event — no stream sync
-void launch_scan_async(GrowCtx& ctx, const torch::Tensor& hists_i64,
-                       SplitJob& job) {
-  const long nh = hists_i64.size(0);
-  const long nf_pad = hists_i64.size(1);
-  auto fopt = torch::TensorOptions()
-                  .dtype(torch::kFloat32).device(hists_i64.device());
-  auto scratch = torch::empty({nh, nf_pad, 6}, fopt);
-  auto out = torch::empty({nh, 6}, fopt);
+// launch the fused sibling subtract + scan (parent undefined: scan `small`
+// alone, the root); the per-feature records land in a pinned host buffer
+// behind an event — no stream sync, the arg-max over features is the host's
+void launch_scan_async(GrowCtx& ctx, const torch::Tensor& parent,
+                       const torch::Tensor& small, torch::Tensor big,
+                       bool small_is_left, SplitJob& job) {
+  const long nh = parent.defined() ? 2 : 1;
+  const long nf_pad = small.size(0);
+  auto records = torch::empty(
+      {nh, nf_pad, 6},
+      torch::TensorOptions().dtype(torch::kFloat32).device(small.device()));
   const bool* mask = ctx.feat_mask.defined()
                          ? ctx.feat_mask.data_ptr<bool>() : nullptr;
-  launch_split_scan_fixed(
-      (const long long*)hists_i64.data_ptr<int64_t>(), (int)nh, nf_pad,
-      ctx.n_bins, (float)ctx.l1, (float)ctx.l2, (float)ctx.min_data,
-      (float)ctx.min_hess, (float)ctx.min_gain, ctx.nf, mask,
-      scratch.data_ptr<float>(), out.data_ptr<float>(), 1.0 / ctx.scale_g,
-      1.0 / ctx.scale_h, grower_stream());
-  job.scan_host = torch::empty({nh, 6}, torch::TensorOptions()
-                                            .dtype(torch::kFloat32)
-                                            .pinned_memory(true));
-  (void)hipMemcpyAsync(job.scan_host.data_ptr<float>(), out.data_ptr<float>(),
-                       nh * 6 * sizeof(float), hipMemcpyDeviceToHost,
+  launch_sibling_scan(
+      parent.defined() ? (const long long*)parent.data_ptr<int64_t>()
+                       : nullptr,
+      (const long long*)small.data_ptr<int64_t>(),
+      big.defined() ? (long long*)big.data_ptr<int64_t>() : nullptr,
+      small_is_left ? 1 : 0, nf_pad, ctx.n_bins, (float)ctx.l1, (float)ctx.l2,
+      (float)ctx.min_data, (float)ctx.min_hess, ctx.nf, mask,
+      records.data_ptr<float>(), 1.0 / ctx.scale_g, 1.0 / ctx.scale_h,
+      grower_stream());
+  job.scan_host = torch::empty({nh, nf_pad, 6}, torch::TensorOptions()
+                                                    .dtype(torch::kFloat32)
+                                                    .pinned_memory(true));
+  (void)hipMemcpyAsync(job.scan_host.data_ptr<float>(),
+                       records.data_ptr<float>(),
+                       nh * nf_pad * 6 * sizeof(float), hipMemcpyDeviceToHost,
                        grower_stream());
   if (!ctx.cat_feats.empty()) {
     // categorical rows of the reduced histogram ride back with the scan;
     // the sorted one-vs-rest scan runs on host at commit (≤ ncat×256 bins)
     const long ncat = (long)ctx.cat_feats.size();
-    auto cat_rows = hists_i64.index_select(1, ctx.cat_idx_dev).contiguous();
+    const size_t per_hist = (size_t)ncat * ctx.n_bins * 3;
     job.cat_host = torch::empty({nh, ncat, (long)ctx.n_bins, 3},
                                 torch::TensorOptions()
                                     .dtype(torch::kInt64)
                                     .pinned_memory(true));
-    (void)hipMemcpyAsync(job.cat_host.data_ptr<int64_t>(),
-                         cat_rows.data_ptr<int64_t>(),
-                         nh * ncat * ctx.n_bins * 3 * sizeof(int64_t),
-                         hipMemcpyDeviceToHost, grower_stream());
+    for (long h = 0; h < nh; ++h) {
+      const torch::Tensor& src = (h == 0) == small_is_left ? small : big;
+      auto cat_rows = src.index_select(0, ctx.cat_idx_dev).contiguous();
+      (void)hipMemcpyAsync(job.cat_host.data_ptr<int64_t>() + h * per_hist,
+                           cat_rows.data_ptr<int64_t>(),
+                           per_hist * sizeof(int64_t), hipMemcpyDeviceToHost,
+                           grower_stream());
+    }
   }
   (void)hipEventCreateWithFlags(&job.ev, hipEventDisableTiming);
   (void)hipEventRecord(job.ev, grower_stream());
@@ -263,9 +288,16 @@ CatBest cat_scan_host(const GrowCtx& ctx, const int64_t* hist) {
 // Fill a candidate's split from the readbacks: numeric scan row `hi`, then
 // let the categorical best take over iff strictly better (trainer._scan).
 void resolve_best(const GrowCtx& ctx, SplitJob& job, int hi, LeafCand& c) {
-  auto a = job.scan_host.accessor<float, 2>();
-  c.gain = a[hi][0]; c.feat = (int)a[hi][1]; c.bin = (int)a[hi][2];
-  c.GL = a[hi][3]; c.HL = a[hi][4]; c.CL = a[hi][5];
+  // arg-max over the per-feature records, by split_reduce_k's rule: highest
+  // gain, ties to the lowest feature, all -inf -> feature 0's record
+  auto rec = job.scan_host.accessor<float, 3>()[hi];
+  long bf = 0;
+  float best = -INFINITY;
+  for (long f = 0; f < rec.size(0); ++f)
+    if (rec[f][0] > best) { best = rec[f][0]; bf = f; }
+  auto a = rec[bf];
+  c.gain = a[0]; c.feat = (int)a[1]; c.bin = (int)a[2];
+  c.GL = a[3]; c.HL = a[4]; c.CL = a[5];
   c.cats.clear();
   if (!ctx.cat_feats.empty()) {
     const size_t stride =
@@ -303,10 +335,9 @@ void launch_job(GrowCtx& ctx, LeafCand& leaf) {
   launch_partition_arena(
       ctx.pair[src].data_ptr(), ctx.ghq[src].data_ptr(),
       ctx.rowid[src].data_ptr<int>(), ctx.pair[dst].data_ptr(),
-      ctx.ghq[dst].data_ptr(), ctx.rowid[dst].data_ptr<int>(),
-      ctx.dst_idx.data_ptr<int>() + leaf.lo, ctx.n_arena,
+      ctx.ghq[dst].data_ptr(), ctx.rowid[dst].data_ptr<int>(), ctx.n_arena,
       ctx.npairs, leaf.lo, m, leaf.feat, leaf.bin, cat_bits,
-      ctx.scratch.data_ptr<int>(), ctx.total.data_ptr<int>(),
+      ctx.scratch.data_ptr<int>(), ctx.total.data_ptr<int>(), 0, 0,
       grower_stream());
 
   const double CL = leaf.CL, CR = leaf.C - leaf.CL;
@@ -327,10 +358,10 @@ void launch_job(GrowCtx& ctx, LeafCand& leaf) {
                          ctx.total.data_ptr<int>(), sizeof(int),
                          hipMemcpyDeviceToHost, grower_stream());
   }
-  auto hist_big = leaf.hist - hist_small;
+  auto hist_big = hist_slot(ctx, false);
   job->hist_l = left_small ? hist_small : hist_big;
   job->hist_r = left_small ? hist_big : hist_small;
-  launch_scan_async(ctx, torch::stack({job->hist_l, job->hist_r}), *job);
+  launch_scan_async(ctx, leaf.hist, hist_small, hist_big, left_small, *job);
   leaf.job = job;
 }
 
@@ -398,11 +429,15 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
 
   ctx.scratch = torch::empty({4096}, rows_root.options().dtype(torch::kInt32));
   ctx.total = torch::zeros({1}, rows_root.options().dtype(torch::kInt32));
-  // per-leaf segments are disjoint, so one dst_idx array serves concurrent
-  // in-flight splits (indexed at leaf.lo)
-  ctx.dst_idx = torch::empty({ctx.n_arena},
-                             rows_root.options().dtype(torch::kInt32));
   auto i64d = rows_root.options().dtype(torch::kInt64);
+  // one zero fill per tree instead of one per split: root + one small child
+  // per split, with room for the two speculated chains
+  // (slabs capped at 1 GiB each; hist_slot allocates per split beyond that)
+  const long slot_bytes = (long)ctx.npairs * 8 * ctx.n_bins * 3 * 8;
+  const long slots = std::min<long>(ctx.num_leaves + 2,
+                                    std::max<long>(1, (1l << 30) / slot_bytes));
+  ctx.slab_zero = torch::zeros({slots, ctx.npairs * 8, ctx.n_bins, 3}, i64d);
+  ctx.slab_raw = torch::empty({slots, ctx.npairs * 8, ctx.n_bins, 3}, i64d);
   for (int b = 0; b < 2; ++b) {
     ctx.pair[b] = torch::empty({ctx.npairs, ctx.n_arena}, i64d);
     ctx.ghq[b] = torch::empty({ctx.n_arena, 2}, i64d);
@@ -443,7 +478,8 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
   {
     // one-time root scan through the same async machinery
     SplitJob j;
-    launch_scan_async(ctx, root_hist.unsqueeze(0), j);
+    launch_scan_async(ctx, torch::Tensor(), root_hist, torch::Tensor(), true,
+                      j);
     (void)hipEventSynchronize(j.ev);
     resolve_best(ctx, j, 0, *root);
   }
@@ -586,9 +622,90 @@ void allreduce_native(py::object process_group, torch::Tensor t) {
   pg->allreduce(v)->wait();
 }
 
+// preds_col[leaf_rows[i]] += values[leaf of i] in one launch; preds_col may be
+// a strided column view.  leaf_offsets: (n_leaves + 1,) i64, any device.
+void apply_leaf_values(torch::Tensor preds_col, torch::Tensor leaf_rows,
+                       torch::Tensor leaf_offsets, torch::Tensor values) {
+  TORCH_CHECK(preds_col.is_cuda() && preds_col.dim() == 1 &&
+              preds_col.scalar_type() == torch::kFloat32,
+              "preds_col: 1-D f32 device tensor");
+  TORCH_CHECK(leaf_rows.is_cuda() && leaf_rows.is_contiguous() &&
+              leaf_rows.scalar_type() == torch::kInt32,
+              "leaf_rows: contiguous i32 device tensor");
+  TORCH_CHECK(values.is_cuda() && values.is_contiguous() &&
+              values.scalar_type() == torch::kFloat32,
+              "values: contiguous f32 device tensor");
+  TORCH_CHECK(leaf_offsets.scalar_type() == torch::kInt64 &&
+              leaf_offsets.numel() == values.numel() + 1,
+              "leaf_offsets: i64 of n_leaves + 1");
+  auto offs_cpu = leaf_offsets.cpu();
+  const int64_t* oc = offs_cpu.data_ptr<int64_t>();
+  const long n_leaves = values.numel();
+  TORCH_CHECK(oc[0] == 0 && oc[n_leaves] == leaf_rows.numel(),
+              "leaf_offsets must span leaf_rows");
+  for (long l = 0; l < n_leaves; ++l)
+    TORCH_CHECK(oc[l] <= oc[l + 1], "leaf_offsets must be non-decreasing");
+  auto offs = leaf_offsets.to(preds_col.device()).contiguous();
+  launch_apply_leaf_values(preds_col.data_ptr<float>(), preds_col.stride(0),
+                           leaf_rows.data_ptr<int>(),
+                           (const long*)offs.data_ptr<int64_t>(),
+                           (int)n_leaves, values.data_ptr<float>(),
+                           leaf_rows.numel(), grower_stream());
+}
+
+// Test/tuning entry for the arena partition: scatters rows [lo, lo+m) of the
+// src arena into dst (stable left|right) and returns the device left count.
+// chunk / plane_groups = 0 take the launcher's own policy.
+torch::Tensor partition_arena(torch::Tensor pair_src, torch::Tensor ghq_src,
+                              torch::Tensor rowid_src, torch::Tensor pair_dst,
+                              torch::Tensor ghq_dst, torch::Tensor rowid_dst,
+                              long lo, long m, long feature, long thr,
+                              c10::optional<torch::Tensor> cat_bits,
+                              long chunk, long plane_groups) {
+  const long n_arena = pair_src.size(1);
+  const long npairs = pair_src.size(0);
+  TORCH_CHECK(pair_src.is_cuda() && pair_src.is_contiguous() &&
+              pair_src.scalar_type() == torch::kInt64 &&
+              pair_dst.is_contiguous() && pair_dst.sizes() == pair_src.sizes(),
+              "pair planes: contiguous (npairs, n_arena) i64");
+  TORCH_CHECK(ghq_src.is_contiguous() && ghq_dst.is_contiguous() &&
+              ghq_src.numel() == 2 * n_arena && ghq_dst.numel() == 2 * n_arena,
+              "ghq: contiguous (n_arena, 2) i64");
+  TORCH_CHECK(rowid_src.is_contiguous() && rowid_dst.is_contiguous() &&
+              rowid_src.numel() == n_arena && rowid_dst.numel() == n_arena,
+              "rowid: contiguous (n_arena,) i32");
+  TORCH_CHECK(lo >= 0 && m >= 0 && lo + m <= n_arena, "range out of bounds");
+  TORCH_CHECK(feature >= 0 && feature < npairs * 8, "feature out of range");
+  const unsigned* bits = nullptr;
+  if (cat_bits.has_value()) {
+    TORCH_CHECK(cat_bits->is_cuda() && cat_bits->is_contiguous() &&
+                cat_bits->scalar_type() == torch::kInt32 &&
+                cat_bits->numel() == 8, "cat_bits: (8,) i32 device");
+    bits = (const unsigned*)cat_bits->data_ptr<int>();
+  }
+  auto i32 = rowid_src.options().dtype(torch::kInt32);
+  auto scratch = torch::empty({4096}, i32);
+  auto total = torch::zeros({1}, i32);
+  launch_partition_arena(pair_src.data_ptr(), ghq_src.data_ptr(),
+                         rowid_src.data_ptr<int>(), pair_dst.data_ptr(),
+                         ghq_dst.data_ptr(), rowid_dst.data_ptr<int>(),
+                         n_arena, (int)npairs, lo, m, (int)feature, (int)thr,
+                         bits, scratch.data_ptr<int>(), total.data_ptr<int>(),
+                         chunk, (int)plane_groups, grower_stream());
+  return total;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grow_tree_native", &grow_tree_native,
         "native leaf-wise GBDT tree growth (numeric features, arena mode)");
+  m.def("apply_leaf_values", &apply_leaf_values,
+        "preds_col[leaf_rows] += per-leaf value, one kernel");
+  m.def("partition_arena", &partition_arena,
+        "arena stable partition (count + fused scatter)", py::arg("pair_src"),
+        py::arg("ghq_src"), py::arg("rowid_src"), py::arg("pair_dst"),
+        py::arg("ghq_dst"), py::arg("rowid_dst"), py::arg("lo"), py::arg("m"),
+        py::arg("feature"), py::arg("thr"), py::arg("cat_bits") = py::none(),
+        py::arg("chunk") = 0, py::arg("plane_groups") = 0);
   m.def("allreduce_native", &allreduce_native,
         "GIL-free c10d all_reduce through the same C++ path as the grower");
 }

@@ -636,121 +636,165 @@ __global__ void part_arena_count_k(const unsigned long long* __restrict__ pair,
   if (threadIdx.x == 0) block_counts[blockIdx.x] = sh[0];
 }
 
-// pass 1: per-row destination index (stable left|right ranks) + move the
-// small payloads (row id + quantized gh); dst_idx drives the plane copies
-__global__ void part_arena_index_k(
+// Fused scatter: per 256-row tile the stable left|right destination rank is
+// computed (ballot/popcount over the split plane) and kept in registers, then
+// row id, gh and the bin planes move straight to it — no dst_idx round trip.
+// blockIdx.y selects a group of `ppg` planes; every group recomputes the
+// ranks from the split plane (8 B/row) and group 0 also moves row id + gh.
+// Each block derives its own exclusive offset and the left total from the
+// count kernel's block_counts (<= 4096 ints, L2-resident), so no scan kernel
+// sits between count and scatter; the kernel boundary orders the two.
+#define PART_PLANE_BATCH 4
+// launcher policy: rows per block, and the leaf size below which the planes
+// are split into y-groups of PART_PLANE_BATCH — see launch_partition_arena
+#define PART_CHUNK_DEFAULT 1024
+#define PART_SPLIT_PLANES_BELOW (1l << 19)
+
+__global__ void part_arena_scatter_k(
     const unsigned long long* __restrict__ pair_src,
     const longlong2* __restrict__ ghq_src, const int* __restrict__ rowid_src,
+    unsigned long long* __restrict__ pair_dst,
     longlong2* __restrict__ ghq_dst, int* __restrict__ rowid_dst,
-    int* __restrict__ dst_idx, long n_arena, long lo, long m, int pf,
-    int jbyte, int thr, const unsigned* __restrict__ cat_bits, long chunk,
-    const int* __restrict__ block_offsets,
-    const int* __restrict__ total_left) {
-  const long start = (long)blockIdx.x * chunk;
-  const long end = min(start + chunk, m);
-  const long nl_total = *total_left;
-  __shared__ long base_l, base_r;
-  __shared__ int wave_l[4], wave_r[4];
-  if (threadIdx.x == 0) {
-    base_l = block_offsets[blockIdx.x];
-    base_r = nl_total + (start - block_offsets[blockIdx.x]);
+    long n_arena, int npairs, int ppg, long lo, long m, int pf, int jbyte,
+    int thr, const unsigned* __restrict__ cat_bits, long chunk,
+    const int* __restrict__ block_counts, int n_blocks,
+    int* __restrict__ total_left) {
+  const int tid = threadIdx.x;
+  const int wid = tid >> 6;
+  const int lane = tid & 63;
+  __shared__ int red_pre[4], red_tot[4];
+  __shared__ int wave_l[2][4];
+  {
+    int pre = 0, tot = 0;
+    for (int b = tid; b < n_blocks; b += blockDim.x) {
+      const int c = block_counts[b];
+      tot += c;
+      if (b < (int)blockIdx.x) pre += c;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      pre += __shfl_down(pre, d);
+      tot += __shfl_down(tot, d);
+    }
+    if (lane == 0) {
+      red_pre[wid] = pre;
+      red_tot[wid] = tot;
+    }
   }
   __syncthreads();
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
+  const long nl_total =
+      (long)red_tot[0] + red_tot[1] + red_tot[2] + red_tot[3];
+  const long start = (long)blockIdx.x * chunk;
+  const long end = min(start + chunk, m);
+  long base_l = (long)red_pre[0] + red_pre[1] + red_pre[2] + red_pre[3];
+  long base_r = nl_total + (start - base_l);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0)
+    *total_left = (int)nl_total;
+
+  const int p0 = (int)blockIdx.y * ppg;
+  const int p1 = min(p0 + ppg, npairs);
+  const bool move_small = blockIdx.y == 0;
   const unsigned long long* split_plane = pair_src + (size_t)pf * n_arena + lo;
-  for (long i0 = start; i0 < end; i0 += blockDim.x) {
-    const long i = i0 + threadIdx.x;
-    bool valid = i < end, left = false;
+  const unsigned long long* src = pair_src + lo;
+  unsigned long long* dst = pair_dst + lo;
+  int par = 0;
+  for (long i0 = start; i0 < end; i0 += blockDim.x, par ^= 1) {
+    const long i = i0 + tid;
+    const bool valid = i < end;
+    bool left = false;
+    unsigned long long wsplit = 0ull;
     if (valid) {
-      const unsigned bv = (unsigned)((split_plane[i] >> (8 * jbyte)) & 0xffull);
+      wsplit = split_plane[i];
+      const unsigned bv = (unsigned)((wsplit >> (8 * jbyte)) & 0xffull);
       left = cat_bits ? (((cat_bits[bv >> 5] >> (bv & 31)) & 1u) != 0u)
                       : (bv <= (unsigned)thr);
     }
     const unsigned long long mask_l = __ballot(valid && left);
-    const unsigned long long mask_r = __ballot(valid && !left);
+    const unsigned long long mask_v = __ballot(valid);
     const unsigned long long lt = (1ull << lane) - 1ull;
-    if (lane == 0) {
-      wave_l[wid] = __popcll(mask_l);
-      wave_r[wid] = __popcll(mask_r);
-    }
-    __syncthreads();
+    if (lane == 0) wave_l[par][wid] = __popcll(mask_l);
+    __syncthreads();  // wave_l is double-buffered: one barrier per tile
     long wl = base_l, wr = base_r;
-    for (int w = 0; w < wid; ++w) {
-      wl += wave_l[w];
-      wr += wave_r[w];
+    int tile_l = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = wave_l[par][w];
+      if (w < wid) {
+        wl += c;
+        wr += 64 - c;  // earlier waves of a tile are always full
+      }
+      tile_l += c;
     }
     if (valid) {
       const long d = left ? wl + __popcll(mask_l & lt)
-                          : wr + __popcll(mask_r & lt);  // relative to lo
-      dst_idx[i] = (int)d;
-      rowid_dst[lo + d] = rowid_src[lo + i];
-      ghq_dst[lo + d] = ghq_src[lo + i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      long al = 0, ar = 0;
-      for (int w = 0; w < 4; ++w) {
-        al += wave_l[w];
-        ar += wave_r[w];
+                          : wr + __popcll(mask_v & ~mask_l & lt);
+      if (move_small) {
+        rowid_dst[lo + d] = rowid_src[lo + i];
+        ghq_dst[lo + d] = ghq_src[lo + i];
       }
-      base_l += al;
-      base_r += ar;
+      for (int p = p0; p < p1; p += PART_PLANE_BATCH) {
+        unsigned long long v[PART_PLANE_BATCH];
+#pragma unroll
+        for (int u = 0; u < PART_PLANE_BATCH; ++u)
+          if (p + u < p1)
+            v[u] = (p + u == pf) ? wsplit : src[(size_t)(p + u) * n_arena + i];
+#pragma unroll
+        for (int u = 0; u < PART_PLANE_BATCH; ++u)
+          if (p + u < p1) dst[(size_t)(p + u) * n_arena + d] = v[u];
+      }
     }
-    __syncthreads();
+    const long tile_n = min((long)blockDim.x, end - i0);
+    base_l += tile_l;
+    base_r += tile_n - tile_l;
   }
-}
-
-// pass 2: plane copies driven by dst_idx — 2-D grid (row-chunk, plane) so
-// all npairs planes stream in parallel with coalesced reads
-__global__ void part_arena_copy_k(
-    const unsigned long long* __restrict__ pair_src,
-    unsigned long long* __restrict__ pair_dst,
-    const int* __restrict__ dst_idx, long n_arena, long lo, long m,
-    long chunk) {
-  const long start = (long)blockIdx.x * chunk;
-  const long end = min(start + chunk, m);
-  const unsigned long long* src = pair_src + (size_t)blockIdx.y * n_arena + lo;
-  unsigned long long* dst = pair_dst + (size_t)blockIdx.y * n_arena + lo;
-  for (long i = start + threadIdx.x; i < end; i += blockDim.x)
-    dst[dst_idx[i]] = src[i];
 }
 
 extern "C" void launch_partition_arena(
     const void* pair_src, const void* ghq_src, const int* rowid_src,
-    void* pair_dst, void* ghq_dst, int* rowid_dst, int* dst_idx,
-    long n_arena, int npairs, long lo, long m, int feature, int thr,
-    const unsigned* cat_bits, int* scratch, int* total_left,
+    void* pair_dst, void* ghq_dst, int* rowid_dst, long n_arena, int npairs,
+    long lo, long m, int feature, int thr, const unsigned* cat_bits,
+    int* scratch, int* total_left, long chunk_override, int groups_override,
     hipStream_t stream) {
   if (m == 0) return;
-  long chunk = 4096;
+  // Policy from tools/partition_sweep.py on MI355X (13 planes, count+scatter,
+  // median us; chunk x plane groups):
+  //   rows     1024x1  1024x4  1024x13  4096x1  4096x13
+  //   2^14      21.5    18.8    18.5     43.9    27.7
+  //   2^16      23.2    19.1    20.1     44.8    29.0
+  //   2^18      29.2    25.9    28.9     60.8    36.8
+  //   2^19      35.6    36.6    48.5
+  //   2^20      65.6    66.4    82.5    106.6    85.0
+  //   2^22     222     235     391      223     261
+  //   10^7     531     550     770      526     657   (4.9 TB/s at 256 B/row)
+  // 256- and 512-row chunks are within 2 us of 1024 up to 2^19 rows and slower
+  // above.  So: 1024-row chunks, groups of 4 planes below 2^19 rows (the
+  // 8 B/row rank recompute per group is cheaper than idle CUs), 1-D above.
+  long chunk = chunk_override > 0 ? chunk_override : PART_CHUNK_DEFAULT;
+  chunk = (chunk + 255) / 256 * 256;
   long blocks = (m + chunk - 1) / chunk;
-  if (blocks > 4096) {
-    chunk = (m + 4095) / 4096;
+  if (blocks > 4096) {  // scratch holds 4096 block counters
+    chunk = ((m + 4095) / 4096 + 255) / 256 * 256;
     blocks = (m + chunk - 1) / chunk;
   }
+  int groups = groups_override > 0
+                   ? groups_override
+                   : (m < PART_SPLIT_PLANES_BELOW
+                          ? (npairs + PART_PLANE_BATCH - 1) / PART_PLANE_BATCH
+                          : 1);
+  if (groups > npairs) groups = npairs;
+  const int ppg = (npairs + groups - 1) / groups;
+  groups = (npairs + ppg - 1) / ppg;
   const int pf = feature / 8, jbyte = feature % 8;
   hipLaunchKernelGGL(part_arena_count_k, dim3((unsigned)blocks), dim3(256),
                      0, stream, (const unsigned long long*)pair_src, n_arena,
                      lo, m, pf, jbyte, thr, cat_bits, chunk, scratch);
-  hipLaunchKernelGGL(part_scan_k, dim3(1), dim3(256), 0, stream, scratch,
-                     (int)blocks, total_left);
-  hipLaunchKernelGGL(part_arena_index_k, dim3((unsigned)blocks), dim3(256),
-                     0, stream, (const unsigned long long*)pair_src,
-                     (const longlong2*)ghq_src, rowid_src,
-                     (longlong2*)ghq_dst, rowid_dst, dst_idx, n_arena, lo, m,
-                     pf, jbyte, thr, cat_bits, chunk, scratch, total_left);
-  long cchunk = 2048;
-  long cblocks = (m + cchunk - 1) / cchunk;
-  if (cblocks > 4096) {
-    cchunk = (m + 4095) / 4096;
-    cblocks = (m + cchunk - 1) / cchunk;
-  }
-  hipLaunchKernelGGL(part_arena_copy_k, dim3((unsigned)cblocks,
-                                             (unsigned)npairs), dim3(256), 0,
+  hipLaunchKernelGGL(part_arena_scatter_k,
+                     dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0,
                      stream, (const unsigned long long*)pair_src,
-                     (unsigned long long*)pair_dst, dst_idx, n_arena, lo, m,
-                     cchunk);
+                     (const longlong2*)ghq_src, rowid_src,
+                     (unsigned long long*)pair_dst, (longlong2*)ghq_dst,
+                     rowid_dst, n_arena, npairs, ppg, lo, m, pf, jbyte, thr,
+                     cat_bits, chunk, scratch, (int)blocks, total_left);
 }
 
 // range-mode histogram over arena segments: rows are CONTIGUOUS [lo+base,
@@ -1079,42 +1123,19 @@ extern "C" void launch_bin_matrix(const float* X, const float* ub, long n,
 // ~50 ms/iter vs 8 ms of GPU time).
 // hist: (n_hists, nf_pad, n_bins, 3); scratch: (n_hists, nf_pad, 6);
 // out: (n_hists, 6) = {gain, feat, bin, GL, HL, CL}.
-// FIXED=true reads int64 fixed-point histograms directly (scales applied
-// in-kernel) — saves the int64→float conversion launches per split.
-template <bool FIXED>
-__global__ void split_scan_k(const void* __restrict__ hist_v, int n_bins,
-                             long nf_pad, float l1, float l2, float min_data,
-                             float min_hess, float min_gain, long nf_real,
-                             const bool* __restrict__ feat_mask,
-                             float* __restrict__ scratch,
-                             double inv_g, double inv_h) {
-  const int f = blockIdx.x;
-  const int hi = blockIdx.y;
-  const int tid = threadIdx.x;
-  float* out = scratch + ((size_t)hi * nf_pad + f) * 6;
-  if (f >= nf_real || (feat_mask && !feat_mask[f])) {
-    if (tid == 0) {
-      out[0] = -INFINITY; out[1] = 0; out[2] = 0;
-      out[3] = 0; out[4] = 0; out[5] = 0;
-    }
-    return;
-  }
-  __shared__ float sg[256], sh[256], sc[256];
+// split_scan_k + split_reduce_k take float histograms (Python grower);
+// sibling_scan_k is the native grower's form: it reads int64 fixed-point
+// histograms directly (scales applied in-kernel), forms the sibling by
+// subtraction and leaves the reduce over features to the host.
+
+// One feature's best split from its per-bin (g, h, count) already staged in
+// LDS as floats (slots >= n_bins zeroed); the caller syncs after staging.
+// Shared by split_scan_k and sibling_scan_k so both scan bit-identically.
+DEV_INLINE void split_scan_feature(float* sg, float* sh, float* sc, int tid,
+                                   int f, int n_bins, float l1, float l2,
+                                   float min_data, float min_hess,
+                                   float* __restrict__ out) {
   const bool in = tid < n_bins;
-  if (FIXED) {
-    const long long* H =
-        (const long long*)hist_v + ((size_t)hi * nf_pad + f) * n_bins * 3;
-    sg[tid] = in ? (float)((double)H[tid * 3 + 0] * inv_g) : 0.0f;
-    sh[tid] = in ? (float)((double)H[tid * 3 + 1] * inv_h) : 0.0f;
-    sc[tid] = in ? (float)H[tid * 3 + 2] : 0.0f;
-  } else {
-    const float* H =
-        (const float*)hist_v + ((size_t)hi * nf_pad + f) * n_bins * 3;
-    sg[tid] = in ? H[tid * 3 + 0] : 0.0f;
-    sh[tid] = in ? H[tid * 3 + 1] : 0.0f;
-    sc[tid] = in ? H[tid * 3 + 2] : 0.0f;
-  }
-  __syncthreads();
   // degenerate feature: every row in ONE bin (e.g. a sparse feature absent
   // from this leaf — all mass in its zero bin) can never split validly;
   // skip the 3 prefix scans + gain pass.  Dominant on wide-sparse shapes
@@ -1182,6 +1203,125 @@ __global__ void split_scan_k(const void* __restrict__ hist_v, int n_bins,
   }
 }
 
+__global__ void split_scan_k(const float* __restrict__ hist, int n_bins,
+                             long nf_pad, float l1, float l2, float min_data,
+                             float min_hess, float min_gain, long nf_real,
+                             const bool* __restrict__ feat_mask,
+                             float* __restrict__ scratch) {
+  const int f = blockIdx.x;
+  const int hi = blockIdx.y;
+  const int tid = threadIdx.x;
+  float* out = scratch + ((size_t)hi * nf_pad + f) * 6;
+  if (f >= nf_real || (feat_mask && !feat_mask[f])) {
+    if (tid == 0) {
+      out[0] = -INFINITY; out[1] = 0; out[2] = 0;
+      out[3] = 0; out[4] = 0; out[5] = 0;
+    }
+    return;
+  }
+  __shared__ float sg[256], sh[256], sc[256];
+  const bool in = tid < n_bins;
+  const float* H = hist + ((size_t)hi * nf_pad + f) * n_bins * 3;
+  sg[tid] = in ? H[tid * 3 + 0] : 0.0f;
+  sh[tid] = in ? H[tid * 3 + 1] : 0.0f;
+  sc[tid] = in ? H[tid * 3 + 2] : 0.0f;
+  __syncthreads();
+  split_scan_feature(sg, sh, sc, tid, f, n_bins, l1, l2, min_data, min_hess,
+                     out);
+}
+
+// Grower epilogue in one launch: blockIdx.y picks the child (0 = left,
+// 1 = right).  The block of the bigger child forms big = parent - small per
+// cell (exact int64), stores it — it becomes that child's LeafCand::hist —
+// and scans it; the block of the smaller child scans `small` as built.  Pad
+// and masked features still get their big cells, so the stored histogram is
+// what a separate subtraction would hold.  With parent == nullptr (root) the
+// grid has one row and `small` is scanned alone.  Records go to
+// (gridDim.y, nf_pad, 6); the arg-max over features is done by the host.
+__global__ void sibling_scan_k(const long long* __restrict__ parent,
+                               const long long* __restrict__ small,
+                               long long* __restrict__ big, int small_is_left,
+                               int n_bins, long nf_pad, float l1, float l2,
+                               float min_data, float min_hess, long nf_real,
+                               const bool* __restrict__ feat_mask,
+                               float* __restrict__ records, double inv_g,
+                               double inv_h) {
+  const int f = blockIdx.x;
+  const int hi = blockIdx.y;
+  const int tid = threadIdx.x;
+  const bool in = tid < n_bins;
+  const bool is_big = parent != nullptr && ((hi == 0) != (small_is_left != 0));
+  const size_t cell = ((size_t)f * n_bins + tid) * 3;
+  long long g = 0, h = 0, c = 0;
+  if (in) {
+    g = small[cell + 0]; h = small[cell + 1]; c = small[cell + 2];
+    if (is_big) {
+      g = parent[cell + 0] - g;
+      h = parent[cell + 1] - h;
+      c = parent[cell + 2] - c;
+      big[cell + 0] = g; big[cell + 1] = h; big[cell + 2] = c;
+    }
+  }
+  float* out = records + ((size_t)hi * nf_pad + f) * 6;
+  if (f >= nf_real || (feat_mask && !feat_mask[f])) {
+    if (tid == 0) {
+      out[0] = -INFINITY; out[1] = 0; out[2] = 0;
+      out[3] = 0; out[4] = 0; out[5] = 0;
+    }
+    return;
+  }
+  __shared__ float sg[256], sh[256], sc[256];
+  sg[tid] = in ? (float)((double)g * inv_g) : 0.0f;
+  sh[tid] = in ? (float)((double)h * inv_h) : 0.0f;
+  sc[tid] = in ? (float)c : 0.0f;
+  __syncthreads();
+  split_scan_feature(sg, sh, sc, tid, f, n_bins, l1, l2, min_data, min_hess,
+                     out);
+}
+
+extern "C" void launch_sibling_scan(const long long* parent,
+                                    const long long* small, long long* big,
+                                    int small_is_left, long nf_pad, int n_bins,
+                                    float l1, float l2, float min_data,
+                                    float min_hess, long nf_real,
+                                    const bool* feat_mask, float* records,
+                                    double inv_g, double inv_h,
+                                    hipStream_t stream) {
+  dim3 grid((unsigned)nf_pad, parent ? 2u : 1u);
+  hipLaunchKernelGGL(sibling_scan_k, grid, dim3(256), 0, stream, parent, small,
+                     big, small_is_left, n_bins, nf_pad, l1, l2, min_data,
+                     min_hess, nf_real, feat_mask, records, inv_g, inv_h);
+}
+
+// preds[row] += value[leaf] for every arena position: thread = position, leaf
+// found by binary search over the (n_leaves + 1) offsets.  Row ids are unique
+// within a tree, so plain stores suffice.
+__global__ void apply_leaf_values_k(float* __restrict__ preds, long stride,
+                                    const int* __restrict__ leaf_rows,
+                                    const long* __restrict__ offsets,
+                                    int n_leaves,
+                                    const float* __restrict__ values, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int lo = 0, hi = n_leaves;  // last leaf l with offsets[l] <= i
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offsets[mid] <= i) lo = mid; else hi = mid;
+  }
+  preds[(size_t)leaf_rows[i] * stride] += values[lo];
+}
+
+extern "C" void launch_apply_leaf_values(float* preds, long stride,
+                                         const int* leaf_rows,
+                                         const long* offsets, int n_leaves,
+                                         const float* values, long n,
+                                         hipStream_t stream) {
+  if (n == 0 || n_leaves == 0) return;
+  hipLaunchKernelGGL(apply_leaf_values_k, dim3((unsigned)((n + 255) / 256)),
+                     dim3(256), 0, stream, preds, stride, leaf_rows, offsets,
+                     n_leaves, values, n);
+}
+
 __global__ void split_reduce_k(const float* __restrict__ scratch, long nf_pad,
                                float* __restrict__ out) {
   const int hi = blockIdx.x;
@@ -1227,25 +1367,9 @@ extern "C" void launch_split_scan(const float* hist, int n_hists, long nf_pad,
                                   const bool* feat_mask, float* scratch,
                                   float* out, hipStream_t stream) {
   dim3 grid1((unsigned)nf_pad, (unsigned)n_hists);
-  hipLaunchKernelGGL((split_scan_k<false>), grid1, dim3(256), 0, stream, hist,
-                     n_bins, nf_pad, l1, l2, min_data, min_hess, min_gain,
-                     nf_real, feat_mask, scratch, 1.0, 1.0);
-  hipLaunchKernelGGL(split_reduce_k, dim3((unsigned)n_hists), dim3(256), 0,
-                     stream, scratch, nf_pad, out);
-}
-
-extern "C" void launch_split_scan_fixed(const long long* hist, int n_hists,
-                                        long nf_pad, int n_bins, float l1,
-                                        float l2, float min_data,
-                                        float min_hess, float min_gain,
-                                        long nf_real, const bool* feat_mask,
-                                        float* scratch, float* out,
-                                        double inv_g, double inv_h,
-                                        hipStream_t stream) {
-  dim3 grid1((unsigned)nf_pad, (unsigned)n_hists);
-  hipLaunchKernelGGL((split_scan_k<true>), grid1, dim3(256), 0, stream, hist,
-                     n_bins, nf_pad, l1, l2, min_data, min_hess, min_gain,
-                     nf_real, feat_mask, scratch, inv_g, inv_h);
+  hipLaunchKernelGGL(split_scan_k, grid1, dim3(256), 0, stream, hist, n_bins,
+                     nf_pad, l1, l2, min_data, min_hess, min_gain, nf_real,
+                     feat_mask, scratch);
   hipLaunchKernelGGL(split_reduce_k, dim3((unsigned)n_hists), dim3(256), 0,
                      stream, scratch, nf_pad, out);
 }
