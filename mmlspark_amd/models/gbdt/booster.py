@@ -71,13 +71,19 @@ class Booster:
         num_iteration overrides."""
         if num_iteration < 0 and getattr(self, "best_iteration", -1) >= 0:
             num_iteration = self.best_iteration + 1
-        if hasattr(X, "densify_chunks"):  # CsrMatrix: bounded-memory scoring
-            outs = [self.predict_raw(chunk, start_iteration, num_iteration)
-                    for _, chunk in X.densify_chunks()]
-            if not outs:
-                base = torch.from_numpy(self.base_score).to(X.device)
-                return base.expand(0, self.n_outputs).clone()
-            return torch.cat(outs, dim=0)
+        if hasattr(X, "densify_chunks"):  # CsrMatrix: scored as CSR, one call
+            base = torch.from_numpy(self.base_score).to(X.device)
+            if not self.trees or X.shape[0] == 0:
+                return base.expand(X.shape[0], self.n_outputs).clone()
+            f = self._flat(X.device)
+            raw = backend.predict_forest_csr(
+                f["feature"], f["threshold"], f["left"], f["right"],
+                f["value"], f["offsets"], X.indptr, X.col, X.val, X.shape[1],
+                self.n_outputs, f["weights"],
+                start_tree=start_iteration * self.n_outputs,
+                num_iteration=num_iteration,
+                cat_offset=f.get("cat_offset"), cat_words=f.get("cat_words"))
+            return raw + base
         X = X if isinstance(X, torch.Tensor) else torch.as_tensor(X, dtype=torch.float32)
         X = X.float()
         if not self.trees:
@@ -103,9 +109,13 @@ class Booster:
         return raw
 
     def predict_leaf(self, X: torch.Tensor) -> torch.Tensor:
-        if hasattr(X, "densify_chunks"):  # CsrMatrix
-            return torch.cat([self.predict_leaf(chunk)
-                              for _, chunk in X.densify_chunks()], dim=0)
+        if hasattr(X, "densify_chunks"):  # CsrMatrix: scored as CSR
+            f = self._flat(X.device)
+            return backend.predict_leaf_csr(
+                f["feature"], f["threshold"], f["left"], f["right"],
+                f["leaf_index"], f["offsets"], X.indptr, X.col, X.val,
+                X.shape[1], cat_offset=f.get("cat_offset"),
+                cat_words=f.get("cat_words"))
         X = X.float()
         f = self._flat(X.device)
         return backend.predict_leaf(f["feature"], f["threshold"], f["left"],
@@ -151,6 +161,14 @@ class Booster:
         (n, n_features+1) for single-output models, (n, K*(n_features+1))
         for multiclass (LightGBM contrib layout).
         GPU path: tree_shap_k kernel (trees deeper than 32 fall back to CPU)."""
+        if hasattr(X, "densify_chunks"):
+            # CsrMatrix: the SHAP output is dense (n, nf+1) by definition, so
+            # densify in the bounded row tiles densify_chunks yields
+            width = self.n_outputs * (self.n_features + 1)
+            outs = [self.predict_contrib(chunk)
+                    for _, chunk in X.densify_chunks()]
+            return (np.concatenate(outs, axis=0) if outs
+                    else np.zeros((0, width), dtype=np.float32))
         depth = self._tree_depth() if self.trees else 0
         K = self.n_outputs
         nf = self.n_features

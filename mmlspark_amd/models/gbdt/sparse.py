@@ -31,7 +31,11 @@ from .binning import BinMapper
 
 class CsrMatrix:
     """Device CSR float matrix (rows compressed). The sparse analog of the
-    dense (n, nf) feature tensor accepted by TrainingSession."""
+    dense (n, nf) feature tensor accepted by TrainingSession.
+
+    Precondition: columns are strictly increasing within each row (the
+    partition and scoring kernels binary-search the row's column segment);
+    from_scipy and from_sparse_vectors sort."""
 
     def __init__(self, indptr: torch.Tensor, col: torch.Tensor,
                  val: torch.Tensor, shape):
@@ -109,7 +113,10 @@ class CsrMatrix:
                          self.val[a:b], (end - start, self.shape[1]))
 
     def densify(self, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Dense (m, nf) float32 for the selected rows (scoring fallback)."""
+        """Dense (m, nf) float32 for the selected rows.  Scoring does not
+        use it (Booster.predict_raw / predict_leaf traverse the CSR rows
+        directly); SHAP contributions, whose output is dense anyway, and
+        tests do."""
         n, nf = self.shape
         if rows is None:
             rows = torch.arange(n, device=self.device)
@@ -125,7 +132,7 @@ class CsrMatrix:
         return out
 
     def densify_chunks(self, chunk: int = 65536):
-        """Iterate (start, dense_chunk) — bounded-memory scoring.  The
+        """Iterate (start, dense_chunk) — bounded-memory dense tiles.  The
         chunk shrinks with feature count so the dense tile stays ≈≤1 GB
         even at 100k features."""
         n, nf = self.shape

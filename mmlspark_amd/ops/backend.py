@@ -201,3 +201,40 @@ def csr_partition_rows(indptr, col, binv, rows, feature, zero_bin,
     bins = cpu_ref.csr_gather_bins(indptr, col, binv, rows, feature, zero_bin)
     mask = bins <= threshold_bin
     return rows[mask], rows[~mask]
+
+
+def predict_forest_csr(node_feature, node_threshold, node_left, node_right,
+                       node_value, tree_offsets, indptr, col, val, n_cols,
+                       n_outputs, tree_weights=None, start_tree=0,
+                       num_iteration=-1, cat_offset=None, cat_words=None):
+    """predict_forest over float CSR rows (col strictly increasing per row;
+    absent feature = 0.0) — the matrix is never densified.  n_cols is the
+    matrix width; a split feature at or beyond it is simply absent."""
+    if val.is_cuda:
+        n_trees = tree_offsets.numel() - 1
+        end_tree = n_trees if num_iteration < 0 else min(
+            n_trees, start_tree + num_iteration * n_outputs)
+        if tree_weights is None:
+            tree_weights = torch.ones(n_trees, dtype=torch.float32,
+                                      device=val.device)
+        return _require_ext().predict_forest_csr(
+            node_feature, node_threshold, node_left, node_right, node_value,
+            tree_offsets, tree_weights, indptr, col, val, n_outputs,
+            start_tree, end_tree, cat_offset, cat_words)
+    return cpu_ref.predict_forest_csr(
+        node_feature, node_threshold, node_left, node_right, node_value,
+        tree_offsets, indptr, col, val, n_cols, n_outputs, tree_weights,
+        start_tree, num_iteration, cat_offset, cat_words)
+
+
+def predict_leaf_csr(node_feature, node_threshold, node_left, node_right,
+                     node_leaf_index, tree_offsets, indptr, col, val, n_cols,
+                     cat_offset=None, cat_words=None):
+    if val.is_cuda:
+        return _require_ext().predict_leaf_csr(
+            node_feature, node_threshold, node_left, node_right,
+            node_leaf_index, tree_offsets, indptr, col, val, cat_offset,
+            cat_words)
+    return cpu_ref.predict_leaf_csr(
+        node_feature, node_threshold, node_left, node_right, node_leaf_index,
+        tree_offsets, indptr, col, val, n_cols, cat_offset, cat_words)

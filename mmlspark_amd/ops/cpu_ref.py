@@ -87,24 +87,41 @@ def predict_forest(node_feature: torch.Tensor, node_threshold: torch.Tensor,
     # traverse ALL trees simultaneously: (n, T) node cursors, one vectorized
     # step per tree level instead of a python loop per tree
     bases = tree_offsets[start_tree:end_tree].long().to(X.device)  # (T,)
+    idx = _traverse(node_feature, node_threshold, node_left, node_right,
+                    bases, n, lambda rows, f: X[rows, f], cat_offset,
+                    cat_words)
+    return _sum_leaf_values(node_value[idx], tree_weights, start_tree,
+                            end_tree, n_outputs)
+
+
+def _traverse(node_feature, node_threshold, node_left, node_right, bases, n,
+              value_of, cat_offset, cat_words) -> torch.Tensor:
+    """Leaf node reached by every (row, tree): (n, T) int64 flat node ids.
+    value_of(rows, f) returns the (n, T) feature values the current nodes
+    test — the only place the row storage (dense / CSR) matters."""
+    T = bases.numel()
     idx = bases.unsqueeze(0).expand(n, T).contiguous()
-    rows = torch.arange(n, device=X.device).unsqueeze(1).expand(n, T)
+    rows = torch.arange(n, device=bases.device).unsqueeze(1).expand(n, T)
     active = node_feature[idx] >= 0
     while bool(active.any()):
         f = node_feature[idx].clamp(min=0).long()
-        xv = X[rows, f]
+        xv = value_of(rows, f)
         go_left = _go_left(xv, idx, node_threshold, cat_offset, cat_words)
         nxt = torch.where(go_left, node_left[idx], node_right[idx]).long()
         idx = torch.where(active, nxt + bases.unsqueeze(0), idx)
         active = node_feature[idx] >= 0
-    vals = node_value[idx]
+    return idx
+
+
+def _sum_leaf_values(vals, tree_weights, start_tree, end_tree, n_outputs):
+    n = vals.shape[0]
     if tree_weights is not None:
         vals = vals * tree_weights[start_tree:end_tree].unsqueeze(0)
-    out = torch.zeros(n, n_outputs, dtype=torch.float32, device=X.device)
+    out = torch.zeros(n, n_outputs, dtype=torch.float32, device=vals.device)
     if n_outputs == 1:
         out[:, 0] = vals.sum(dim=1)
     else:
-        cls = (torch.arange(start_tree, end_tree, device=X.device)
+        cls = (torch.arange(start_tree, end_tree, device=vals.device)
                % n_outputs)
         out.index_add_(1, cls, vals)
     return out
@@ -119,16 +136,74 @@ def predict_leaf(node_feature, node_threshold, node_left, node_right,
     if n_trees == 0 or n == 0:
         return torch.zeros(n, n_trees, dtype=torch.int32, device=X.device)
     bases = tree_offsets[:-1].long().to(X.device)
-    idx = bases.unsqueeze(0).expand(n, n_trees).contiguous()
-    rows = torch.arange(n, device=X.device).unsqueeze(1).expand(n, n_trees)
-    active = node_feature[idx] >= 0
-    while bool(active.any()):
-        f = node_feature[idx].clamp(min=0).long()
-        xv = X[rows, f]
-        go_left = _go_left(xv, idx, node_threshold, cat_offset, cat_words)
-        nxt = torch.where(go_left, node_left[idx], node_right[idx]).long()
-        idx = torch.where(active, nxt + bases.unsqueeze(0), idx)
-        active = node_feature[idx] >= 0
+    idx = _traverse(node_feature, node_threshold, node_left, node_right,
+                    bases, n, lambda rows, f: X[rows, f], cat_offset,
+                    cat_words)
+    return node_leaf_index[idx].to(torch.int32)
+
+
+def _csr_value_of(indptr, col, val, n_cols):
+    """Row accessor over CSR storage for _traverse, without densifying:
+    key = row * n_cols + col is globally sorted (rows ascend, columns are
+    strictly increasing within a row), so searchsorted finds the slot and an
+    equality check decides the hit.  Absent entries — and split features at
+    or beyond n_cols, whose key would alias the next row — read 0.0."""
+    n = indptr.numel() - 1
+    counts = indptr[1:] - indptr[:-1]
+    erow = torch.repeat_interleave(
+        torch.arange(n, device=indptr.device), counts)
+    stride = max(int(n_cols), 1)
+    keys = erow * stride + col.long()
+    nnz = keys.numel()
+
+    def value_of(rows, f):
+        if nnz == 0:
+            return torch.zeros(rows.shape, dtype=torch.float32,
+                               device=val.device)
+        q = (rows * stride + f).contiguous()
+        slot = torch.searchsorted(keys, q).clamp(max=nnz - 1)
+        hit = (keys[slot] == q) & (f < n_cols)
+        return torch.where(hit, val[slot], torch.zeros((), dtype=val.dtype,
+                                                       device=val.device))
+    return value_of
+
+
+def predict_forest_csr(node_feature, node_threshold, node_left, node_right,
+                       node_value, tree_offsets, indptr, col, val, n_cols,
+                       n_outputs, tree_weights=None, start_tree=0,
+                       num_iteration=-1, cat_offset=None,
+                       cat_words=None) -> torch.Tensor:
+    """predict_forest over CSR rows (indptr int64 (n+1,), col int32 strictly
+    increasing per row, val f32): an absent feature is 0.0, a stored value
+    (NaN, 0.0, negative) is itself.  Same traversal and accumulation as the
+    dense reference; the matrix is never densified."""
+    n = indptr.numel() - 1
+    n_trees = tree_offsets.numel() - 1
+    end_tree = n_trees if num_iteration < 0 else min(
+        n_trees, start_tree + num_iteration * n_outputs)
+    if end_tree - start_tree <= 0 or n == 0:
+        return torch.zeros(n, n_outputs, dtype=torch.float32,
+                           device=val.device)
+    bases = tree_offsets[start_tree:end_tree].long().to(val.device)
+    idx = _traverse(node_feature, node_threshold, node_left, node_right,
+                    bases, n, _csr_value_of(indptr, col, val, n_cols),
+                    cat_offset, cat_words)
+    return _sum_leaf_values(node_value[idx], tree_weights, start_tree,
+                            end_tree, n_outputs)
+
+
+def predict_leaf_csr(node_feature, node_threshold, node_left, node_right,
+                     node_leaf_index, tree_offsets, indptr, col, val, n_cols,
+                     cat_offset=None, cat_words=None) -> torch.Tensor:
+    """predict_leaf over CSR rows: (n, n_trees) int32, never densified."""
+    n = indptr.numel() - 1
+    n_trees = tree_offsets.numel() - 1
+    if n_trees == 0 or n == 0:
+        return torch.zeros(n, n_trees, dtype=torch.int32, device=val.device)
+    bases = tree_offsets[:-1].long().to(val.device)
+    idx = _traverse(node_feature, node_threshold, node_left, node_right,
+                    bases, n, _csr_value_of(indptr, col, val, n_cols),
+                    cat_offset, cat_words)
     return node_leaf_index[idx].to(torch.int32)
 
 

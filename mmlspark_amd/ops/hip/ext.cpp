@@ -18,6 +18,15 @@ void launch_predict_forest(const int*, const float*, const int*, const int*,
 void launch_predict_leaf(const int*, const float*, const int*, const int*,
                          const int*, const long*, const float*, long, int,
                          int*, int, const int*, const unsigned*, hipStream_t);
+void launch_predict_forest_csr(const int*, const float*, const int*,
+                               const int*, const float*, const long*,
+                               const float*, const long*, const int*,
+                               const float*, long, float*, int, int, int,
+                               const int*, const unsigned*, hipStream_t);
+void launch_predict_leaf_csr(const int*, const float*, const int*, const int*,
+                             const int*, const long*, const long*, const int*,
+                             const float*, long, int*, int, const int*,
+                             const unsigned*, hipStream_t);
 void launch_bin_matrix(const float*, const float*, long, int, int, int, void*,
                        hipStream_t);
 void launch_hist_build_fixed(const void*, long, const int*, long, const float*,
@@ -175,6 +184,77 @@ torch::Tensor predict_leaf(torch::Tensor feat, torch::Tensor thr,
                       leaf_index.data_ptr<int>(), offsets.data_ptr<long>(),
                       X.data_ptr<float>(), n, (int)nf, out.data_ptr<int>(),
                       (int)n_trees, co, cw, cur_stream());
+  return out;
+}
+
+// CSR-row scoring: the row is (indptr, col, xval) instead of X + row*nf.
+// col must be strictly increasing within a row (CsrMatrix's precondition).
+static long check_csr_rows(const torch::Tensor& indptr,
+                           const torch::Tensor& col,
+                           const torch::Tensor& xval) {
+  CHECK_DEV(indptr); CHECK_CONTIG(indptr);
+  CHECK_DEV(col); CHECK_CONTIG(col);
+  CHECK_DEV(xval); CHECK_CONTIG(xval);
+  TORCH_CHECK(indptr.dtype() == torch::kInt64, "indptr must be int64");
+  TORCH_CHECK(col.dtype() == torch::kInt32, "col must be int32");
+  TORCH_CHECK(xval.dtype() == torch::kFloat32, "xval must be float32");
+  TORCH_CHECK(indptr.dim() == 1 && indptr.numel() >= 1,
+              "indptr must hold n+1 row offsets");
+  TORCH_CHECK(col.numel() == xval.numel(),
+              "col and xval must have one entry per stored value");
+  return indptr.numel() - 1;
+}
+
+torch::Tensor predict_forest_csr(torch::Tensor feat, torch::Tensor thr,
+                                 torch::Tensor left, torch::Tensor right,
+                                 torch::Tensor val, torch::Tensor offsets,
+                                 torch::Tensor tw, torch::Tensor indptr,
+                                 torch::Tensor col, torch::Tensor xval,
+                                 long n_outputs, long t0, long t1,
+                                 c10::optional<torch::Tensor> cat_offset,
+                                 c10::optional<torch::Tensor> cat_words) {
+  const long n = check_csr_rows(indptr, col, xval);
+  CHECK_DEV(feat); CHECK_CONTIG(feat);
+  CHECK_DEV(offsets); CHECK_CONTIG(offsets);
+  TORCH_CHECK(offsets.dtype() == torch::kInt64, "offsets must be int64");
+  TORCH_CHECK(n_outputs >= 1, "n_outputs must be positive");
+  const long n_trees = offsets.numel() - 1;
+  auto out = torch::zeros({n, n_outputs},
+                          xval.options().dtype(torch::kFloat32));
+  if (n == 0 || n_trees <= 0 || t1 <= t0) return out;
+  TORCH_CHECK(t0 >= 0 && t1 <= n_trees, "tree window outside the forest");
+  TORCH_CHECK(tw.numel() >= t1, "one weight per tree");
+  auto [co, cw] = cat_ptrs(cat_offset, cat_words);
+  launch_predict_forest_csr(
+      feat.data_ptr<int>(), thr.data_ptr<float>(), left.data_ptr<int>(),
+      right.data_ptr<int>(), val.data_ptr<float>(), offsets.data_ptr<long>(),
+      tw.data_ptr<float>(), indptr.data_ptr<long>(), col.data_ptr<int>(),
+      xval.data_ptr<float>(), n, out.data_ptr<float>(), (int)n_outputs,
+      (int)t0, (int)t1, co, cw, cur_stream());
+  return out;
+}
+
+torch::Tensor predict_leaf_csr(torch::Tensor feat, torch::Tensor thr,
+                               torch::Tensor left, torch::Tensor right,
+                               torch::Tensor leaf_index, torch::Tensor offsets,
+                               torch::Tensor indptr, torch::Tensor col,
+                               torch::Tensor xval,
+                               c10::optional<torch::Tensor> cat_offset,
+                               c10::optional<torch::Tensor> cat_words) {
+  const long n = check_csr_rows(indptr, col, xval);
+  CHECK_DEV(feat); CHECK_CONTIG(feat);
+  CHECK_DEV(offsets); CHECK_CONTIG(offsets);
+  TORCH_CHECK(offsets.dtype() == torch::kInt64, "offsets must be int64");
+  const long n_trees = offsets.numel() - 1;
+  auto out = torch::zeros({n, n_trees}, xval.options().dtype(torch::kInt32));
+  if (n == 0 || n_trees <= 0) return out;
+  auto [co, cw] = cat_ptrs(cat_offset, cat_words);
+  launch_predict_leaf_csr(
+      feat.data_ptr<int>(), thr.data_ptr<float>(), left.data_ptr<int>(),
+      right.data_ptr<int>(), leaf_index.data_ptr<int>(),
+      offsets.data_ptr<long>(), indptr.data_ptr<long>(), col.data_ptr<int>(),
+      xval.data_ptr<float>(), n, out.data_ptr<int>(), (int)n_trees, co, cw,
+      cur_stream());
   return out;
 }
 
@@ -410,6 +490,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fixed-point u64 histogram (fast LDS integer atomics)");
   m.def("predict_forest", &predict_forest, "GBDT ensemble raw scores");
   m.def("predict_leaf", &predict_leaf, "GBDT per-tree leaf indices");
+  m.def("predict_forest_csr", &predict_forest_csr,
+        "GBDT ensemble raw scores over CSR rows (no densify)");
+  m.def("predict_leaf_csr", &predict_leaf_csr,
+        "GBDT per-tree leaf indices over CSR rows (no densify)");
   m.def("bin_matrix", &bin_matrix, "quantile binning to interleaved uint8");
   m.def("split_scan", &split_scan, "fused best-split over sibling histograms");
   m.def("partition_rows", &partition_rows,

@@ -1075,6 +1075,196 @@ extern "C" void launch_predict_leaf(const int* feat, const float* thr,
                      nf, out, n_trees, catoff, catw);
 }
 
+// ------------------------------------------------- forest predict, CSR rows
+// Same contract as predict_forest_k / predict_leaf_k, but the row is a CSR
+// segment (indptr int64, col int32 strictly increasing per row, val f32)
+// instead of X + row*nf: an absent feature reads as 0.0f, a stored value
+// (NaN, 0.0, negative, category >= 256) reads as itself.  The accumulate
+// statements are the dense kernels' own, so scores are bit-identical to the
+// dense kernels on the densified matrix.
+//
+// csr_row_values: U lookups in one row [lo, hi).  Branch-free lower bound —
+// the step count depends only on the row length, so the U searches advance
+// in lockstep and their col loads overlap (the 4-tree interleave keeps four
+// search chains in flight per lane).  p ends on the last entry with
+// col <= f (or on lo); every load is inside [lo, hi).  A feature id that no
+// row stores — negative (finished chain) or beyond the matrix width — simply
+// finds nothing.
+template <int U>
+DEV_INLINE void csr_row_values(const int* __restrict__ col,
+                               const float* __restrict__ xval, long lo,
+                               long hi, const int (&f)[U], float (&xv)[U]) {
+  long n = hi - lo;
+  if (n <= 0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) xv[u] = 0.0f;
+    return;
+  }
+  long p[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) p[u] = lo;
+  while (n > 1) {
+    const long half = n >> 1;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      p[u] = col[p[u] + half] <= f[u] ? p[u] + half : p[u];
+    n -= half;
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float v = xval[p[u]];
+    xv[u] = col[p[u]] == f[u] ? v : 0.0f;
+  }
+}
+
+DEV_INLINE float csr_row_value(const int* __restrict__ col,
+                               const float* __restrict__ xval, long lo,
+                               long hi, int f) {
+  const int fa[1] = {f};
+  float xv[1];
+  csr_row_values<1>(col, xval, lo, hi, fa, xv);
+  return xv[0];
+}
+
+__global__ void predict_forest_csr_k(const int* __restrict__ feat,
+                                     const float* __restrict__ thr,
+                                     const int* __restrict__ left,
+                                     const int* __restrict__ right,
+                                     const float* __restrict__ val,
+                                     const long* __restrict__ offsets,
+                                     const float* __restrict__ tw,
+                                     const long* __restrict__ indptr,
+                                     const int* __restrict__ col,
+                                     const float* __restrict__ xval, long n,
+                                     float* __restrict__ out, int n_outputs,
+                                     int t0, int t1,
+                                     const int* __restrict__ catoff,
+                                     const unsigned* __restrict__ catw) {
+  const long row0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long row = row0; row < n; row += stride) {
+    const long lo = indptr[row], hi = indptr[row + 1];
+    if (n_outputs == 1) {
+      float acc = 0.0f;
+      int t = t0;
+      for (; t + 3 < t1; t += 4) {
+        long idx[4];
+        long base[4];
+        bool done[4] = {false, false, false, false};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          base[u] = offsets[t + u];
+          idx[u] = base[u];
+          done[u] = feat[idx[u]] < 0;
+        }
+        while (!(done[0] & done[1] & done[2] & done[3])) {
+          int f[4];
+          float xv[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) f[u] = feat[idx[u]];  // < 0 when done
+          csr_row_values<4>(col, xval, lo, hi, f, xv);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (!done[u]) {
+              idx[u] = base[u]
+                       + (go_left_node(xv[u], idx[u], thr, catoff, catw)
+                              ? left[idx[u]] : right[idx[u]]);
+              done[u] = feat[idx[u]] < 0;
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc += tw[t + u] * val[idx[u]];
+      }
+      for (; t < t1; ++t) {
+        long idx = offsets[t];
+        const long base = idx;
+        int f = feat[idx];
+        while (f >= 0) {
+          const float xv = csr_row_value(col, xval, lo, hi, f);
+          idx = base + (go_left_node(xv, idx, thr, catoff, catw) ? left[idx]
+                                                                 : right[idx]);
+          f = feat[idx];
+        }
+        acc += tw[t] * val[idx];
+      }
+      out[row] += acc;
+    } else {
+      for (int t = t0; t < t1; ++t) {
+        long idx = offsets[t];
+        const long base = idx;
+        int f = feat[idx];
+        while (f >= 0) {
+          const float xv = csr_row_value(col, xval, lo, hi, f);
+          idx = base + (go_left_node(xv, idx, thr, catoff, catw) ? left[idx]
+                                                                 : right[idx]);
+          f = feat[idx];
+        }
+        out[row * n_outputs + (t % n_outputs)] += tw[t] * val[idx];
+      }
+    }
+  }
+}
+
+extern "C" void launch_predict_forest_csr(
+    const int* feat, const float* thr, const int* left, const int* right,
+    const float* val, const long* offsets, const float* tw,
+    const long* indptr, const int* col, const float* xval, long n, float* out,
+    int n_outputs, int t0, int t1, const int* catoff, const unsigned* catw,
+    hipStream_t stream) {
+  if (n == 0 || t1 <= t0) return;
+  long blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(predict_forest_csr_k, dim3((unsigned)blocks), dim3(256),
+                     0, stream, feat, thr, left, right, val, offsets, tw,
+                     indptr, col, xval, n, out, n_outputs, t0, t1, catoff,
+                     catw);
+}
+
+__global__ void predict_leaf_csr_k(const int* __restrict__ feat,
+                                   const float* __restrict__ thr,
+                                   const int* __restrict__ left,
+                                   const int* __restrict__ right,
+                                   const int* __restrict__ leaf_index,
+                                   const long* __restrict__ offsets,
+                                   const long* __restrict__ indptr,
+                                   const int* __restrict__ col,
+                                   const float* __restrict__ xval, long n,
+                                   int* __restrict__ out, int n_trees,
+                                   const int* __restrict__ catoff,
+                                   const unsigned* __restrict__ catw) {
+  const long row0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long row = row0; row < n; row += stride) {
+    const long lo = indptr[row], hi = indptr[row + 1];
+    for (int t = 0; t < n_trees; ++t) {
+      long idx = offsets[t];
+      const long base = idx;
+      int f = feat[idx];
+      while (f >= 0) {
+        const float xv = csr_row_value(col, xval, lo, hi, f);
+        idx = base + (go_left_node(xv, idx, thr, catoff, catw) ? left[idx]
+                                                               : right[idx]);
+        f = feat[idx];
+      }
+      out[row * n_trees + t] = leaf_index[idx];
+    }
+  }
+}
+
+extern "C" void launch_predict_leaf_csr(
+    const int* feat, const float* thr, const int* left, const int* right,
+    const int* leaf_index, const long* offsets, const long* indptr,
+    const int* col, const float* xval, long n, int* out, int n_trees,
+    const int* catoff, const unsigned* catw, hipStream_t stream) {
+  if (n == 0 || n_trees <= 0) return;
+  long blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(predict_leaf_csr_k, dim3((unsigned)blocks), dim3(256), 0,
+                     stream, feat, thr, left, right, leaf_index, offsets,
+                     indptr, col, xval, n, out, n_trees, catoff, catw);
+}
+
 // ----------------------------------------------------------------- binning
 // X: (n, nf) f32 row-major; ub: (nf, n_bins-1) ascending; out: (ngroups, n) uchar4
 __global__ void bin_matrix_k(const float* __restrict__ X,
