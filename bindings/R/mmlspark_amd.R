@@ -699,7 +699,7 @@ ml_identify_faces <- function(url = NULL, subscriptionKey = NULL, subscriptionKe
   stage
 }
 
-ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = NULL, moduleBytes = NULL, device = NULL, modelName = NULL, cutOutputLayers = NULL, imageSize = NULL, modelPath = NULL) {
+ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = NULL, moduleBytes = NULL, device = NULL, modelName = NULL, cutOutputLayers = NULL, imageSize = NULL, modelPath = NULL, decodeOnDevice = NULL) {
   stage <- mmlspark_amd$models$image_featurizer$ImageFeaturizer()
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(outputCol)) stage$set("outputCol", outputCol)
@@ -710,6 +710,7 @@ ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = N
   if (!is.null(cutOutputLayers)) stage$set("cutOutputLayers", cutOutputLayers)
   if (!is.null(imageSize)) stage$set("imageSize", imageSize)
   if (!is.null(modelPath)) stage$set("modelPath", modelPath)
+  if (!is.null(decodeOnDevice)) stage$set("decodeOnDevice", decodeOnDevice)
   stage
 }
 

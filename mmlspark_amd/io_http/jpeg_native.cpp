@@ -8,7 +8,15 @@
 // the Python codec's scipy idctn so both decoders agree to ±1 LSB.
 // Completes the reference's ImageUtils decode surface
 // (core/.../core/image/ImageUtils.scala) at native speed.
+//
+// The parser and entropy decoder live in jpeg_parse.h (no torch dependency,
+// shared with tools/jpeg_parse_fuzz.cpp).  This file holds the two entry
+// points: decode_jpeg reconstructs pixels on the host; decode_jpeg_coefficients
+// stops after entropy decoding and exports the coefficient planes for the
+// device reconstruction in ops/hip/image_kernels.hip.
 #include <torch/extension.h>
+
+#include "jpeg_parse.h"
 
 #include <cmath>
 #include <cstdint>
@@ -16,371 +24,9 @@
 #include <stdexcept>
 #include <vector>
 
+using namespace jpegparse;
+
 namespace {
-
-struct HuffTable {
-  // canonical decode tables (F.2.2.3)
-  int32_t mincode[17];
-  int32_t maxcode[18];
-  int32_t valptr[17];
-  uint8_t vals[256];
-  bool present = false;
-
-  void build(const uint8_t* bits, const uint8_t* values, int nvals) {
-    std::memcpy(vals, values, nvals);
-    int code = 0, k = 0;
-    for (int l = 1; l <= 16; ++l) {
-      valptr[l] = k;
-      mincode[l] = code;
-      code += bits[l - 1];
-      k += bits[l - 1];
-      maxcode[l] = code - 1;
-      if (bits[l - 1] == 0) maxcode[l] = -1;
-      code <<= 1;
-    }
-    maxcode[17] = 0x7fffffff;
-    present = true;
-  }
-};
-
-struct BitReader {
-  const uint8_t* data;
-  size_t n;
-  size_t pos = 0;
-  uint32_t bitbuf = 0;
-  int bitcnt = 0;
-  bool hit_marker = false;  // stopped at a non-RST marker
-
-  BitReader(const uint8_t* d, size_t len) : data(d), n(len) {}
-
-  int next_byte() {
-    // returns -1 at a non-RST marker (end of entropy data)
-    while (pos < n) {
-      uint8_t b = data[pos];
-      if (b != 0xFF) { ++pos; return b; }
-      if (pos + 1 >= n) { hit_marker = true; return -1; }
-      uint8_t m = data[pos + 1];
-      if (m == 0x00) { pos += 2; return 0xFF; }
-      if (m >= 0xD0 && m <= 0xD7) { hit_marker = true; return -1; }
-      hit_marker = true;
-      return -1;  // real marker: stop (pos stays at the 0xFF)
-    }
-    hit_marker = true;
-    return -1;
-  }
-
-  int read_bit() {
-    if (bitcnt == 0) {
-      int b = next_byte();
-      if (b < 0) return 0;  // pad with 0s past the marker (spec behaviour)
-      bitbuf = (uint32_t)b;
-      bitcnt = 8;
-    }
-    bitcnt--;
-    return (bitbuf >> bitcnt) & 1;
-  }
-
-  int read_bits(int nb) {
-    int v = 0;
-    for (int i = 0; i < nb; ++i) v = (v << 1) | read_bit();
-    return v;
-  }
-
-  void align_and_skip_rst() {
-    bitcnt = 0;
-    // skip to and over the RSTn marker
-    while (pos + 1 < n) {
-      if (data[pos] == 0xFF && data[pos + 1] >= 0xD0 &&
-          data[pos + 1] <= 0xD7) {
-        pos += 2;
-        hit_marker = false;
-        return;
-      }
-      ++pos;
-    }
-  }
-};
-
-inline int extend(int v, int t) {
-  return (t && v < (1 << (t - 1))) ? v - (1 << t) + 1 : v;
-}
-
-int decode_huff(BitReader& br, const HuffTable& h) {
-  int code = br.read_bit();
-  int l = 1;
-  while (code > h.maxcode[l]) {
-    code = (code << 1) | br.read_bit();
-    if (++l > 16) throw std::runtime_error("bad huffman code");
-  }
-  return h.vals[h.valptr[l] + code - h.mincode[l]];
-}
-
-struct Component {
-  int id = 0, h = 1, v = 1, tq = 0;
-  int td = 0, ta = 0;       // current scan's tables
-  int bw = 0, bh = 0;        // blocks across / down (full, MCU padded)
-  std::vector<int32_t> coef; // bw*bh blocks × 64, zigzag order
-};
-
-const int ZIGZAG[64] = {
-    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-    12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-    58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-struct Decoder {
-  const uint8_t* data;
-  size_t n;
-  size_t pos = 2;
-  int W = 0, H = 0;
-  bool progressive = false;
-  int hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
-  std::vector<Component> comps;
-  uint16_t qt[4][64] = {};
-  HuffTable dc[4], ac[4];
-  int dri = 0;
-  int eobrun = 0;
-
-  explicit Decoder(const uint8_t* d, size_t len) : data(d), n(len) {}
-
-  uint16_t u16(size_t p) const { return (data[p] << 8) | data[p + 1]; }
-
-  void parse() {
-    if (n < 4 || data[0] != 0xFF || data[1] != 0xD8)
-      throw std::runtime_error("not a JPEG");
-    bool got_frame = false;
-    while (pos + 4 <= n) {
-      if (data[pos] != 0xFF) { ++pos; continue; }
-      uint8_t m = data[pos + 1];
-      pos += 2;
-      if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-      if (m == 0xD9) break;  // EOI
-      size_t seglen = u16(pos);
-      size_t segend = pos + seglen;
-      const uint8_t* seg = data + pos + 2;
-      size_t sn = seglen - 2;
-      if (m == 0xDB) {
-        size_t o = 0;
-        while (o < sn) {
-          int pq = seg[o] >> 4, tq2 = seg[o] & 15;
-          ++o;
-          for (int k = 0; k < 64; ++k) {
-            if (pq) { qt[tq2][k] = (seg[o] << 8) | seg[o + 1]; o += 2; }
-            else qt[tq2][k] = seg[o + k];
-          }
-          if (!pq) o += 64;
-        }
-      } else if (m == 0xC4) {
-        size_t o = 0;
-        while (o + 17 <= sn) {
-          int tc = seg[o] >> 4, th = seg[o] & 15;
-          const uint8_t* bits = seg + o + 1;
-          int nv = 0;
-          for (int i = 0; i < 16; ++i) nv += bits[i];
-          (tc ? ac[th] : dc[th]).build(bits, seg + o + 17, nv);
-          o += 17 + nv;
-        }
-      } else if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
-        progressive = (m == 0xC2);
-        H = (seg[1] << 8) | seg[2];
-        W = (seg[3] << 8) | seg[4];
-        int nc = seg[5];
-        comps.resize(nc);
-        for (int i = 0; i < nc; ++i) {
-          comps[i].id = seg[6 + 3 * i];
-          comps[i].h = seg[7 + 3 * i] >> 4;
-          comps[i].v = seg[7 + 3 * i] & 15;
-          comps[i].tq = seg[8 + 3 * i];
-        }
-        hmax = vmax = 1;
-        for (auto& c : comps) { hmax = std::max(hmax, c.h);
-                                vmax = std::max(vmax, c.v); }
-        mcux = (W + 8 * hmax - 1) / (8 * hmax);
-        mcuy = (H + 8 * vmax - 1) / (8 * vmax);
-        for (auto& c : comps) {
-          c.bw = mcux * c.h;
-          c.bh = mcuy * c.v;
-          c.coef.assign((size_t)c.bw * c.bh * 64, 0);
-        }
-        got_frame = true;
-      } else if (m == 0xC3 || (m >= 0xC5 && m <= 0xCF && m != 0xC8)) {
-        throw std::runtime_error("unsupported SOF marker");
-      } else if (m == 0xDD) {
-        dri = (seg[0] << 8) | seg[1];
-      } else if (m == 0xDA) {
-        if (!got_frame) throw std::runtime_error("SOS before SOF");
-        int ns = seg[0];
-        std::vector<int> sel;
-        for (int i = 0; i < ns; ++i) {
-          int cs = seg[1 + 2 * i], tda = seg[2 + 2 * i];
-          for (size_t ci = 0; ci < comps.size(); ++ci)
-            if (comps[ci].id == cs) {
-              comps[ci].td = tda >> 4;
-              comps[ci].ta = tda & 15;
-              sel.push_back((int)ci);
-            }
-        }
-        int Ss = seg[1 + 2 * ns], Se = seg[2 + 2 * ns];
-        int Ah = seg[3 + 2 * ns] >> 4, Al = seg[3 + 2 * ns] & 15;
-        pos = segend;
-        decode_scan(sel, Ss, Se, Ah, Al);
-        continue;  // pos updated past the entropy data
-      }
-      pos = segend;
-    }
-  }
-
-  void decode_scan(const std::vector<int>& sel, int Ss, int Se, int Ah,
-                   int Al) {
-    BitReader br(data, n);
-    br.pos = pos;
-    eobrun = 0;
-    std::vector<int> pred(comps.size(), 0);
-
-    const bool interleaved = sel.size() > 1;
-    long unit_count = 0;
-    auto maybe_rst = [&]() {
-      if (dri && unit_count && unit_count % dri == 0) {
-        br.align_and_skip_rst();
-        std::fill(pred.begin(), pred.end(), 0);
-        eobrun = 0;
-      }
-    };
-
-    if (interleaved || (!progressive && sel.size() == comps.size() &&
-                        comps.size() > 1)) {
-      for (int my = 0; my < mcuy; ++my)
-        for (int mx = 0; mx < mcux; ++mx) {
-          maybe_rst();
-          for (int ci : sel) {
-            Component& c = comps[ci];
-            for (int vy = 0; vy < c.v; ++vy)
-              for (int vx = 0; vx < c.h; ++vx) {
-                int bx = mx * c.h + vx, by = my * c.v + vy;
-                int32_t* blk = &c.coef[((size_t)by * c.bw + bx) * 64];
-                decode_block(br, c, blk, pred[ci], Ss, Se, Ah, Al);
-              }
-          }
-          ++unit_count;
-        }
-    } else {
-      // non-interleaved: one component, block raster over ITS OWN grid
-      int ci = sel[0];
-      Component& c = comps[ci];
-      int bw = (W * c.h + 8 * hmax - 1) / (8 * hmax);
-      int bh = (H * c.v + 8 * vmax - 1) / (8 * vmax);
-      for (int by = 0; by < bh; ++by)
-        for (int bx = 0; bx < bw; ++bx) {
-          maybe_rst();
-          int32_t* blk = &c.coef[((size_t)by * c.bw + bx) * 64];
-          decode_block(br, c, blk, pred[ci], Ss, Se, Ah, Al);
-          ++unit_count;
-        }
-    }
-    // advance main parse position to the marker the reader stopped at
-    pos = br.pos;
-  }
-
-  void decode_block(BitReader& br, Component& c, int32_t* blk, int& pred,
-                    int Ss, int Se, int Ah, int Al) {
-    if (!progressive) {
-      // baseline: full block (F.2.2)
-      int t = decode_huff(br, dc[c.td]);
-      pred += extend(br.read_bits(t), t);
-      blk[0] = pred;
-      int k = 1;
-      while (k < 64) {
-        int rs = decode_huff(br, ac[c.ta]);
-        int r = rs >> 4, s = rs & 15;
-        if (rs == 0x00) break;
-        if (rs == 0xF0) { k += 16; continue; }
-        k += r;
-        if (k > 63) break;
-        blk[k] = extend(br.read_bits(s), s);
-        ++k;
-      }
-      return;
-    }
-    if (Ss == 0) {
-      if (Ah == 0) {  // DC first (G.2.1)
-        int t = decode_huff(br, dc[c.td]);
-        pred += extend(br.read_bits(t), t);
-        blk[0] = pred << Al;
-      } else {        // DC refinement
-        if (br.read_bit()) blk[0] |= (1 << Al);
-      }
-      return;
-    }
-    // AC scans (single component)
-    if (Ah == 0) {  // AC first (G.2.2)
-      if (eobrun > 0) { --eobrun; return; }
-      int k = Ss;
-      while (k <= Se) {
-        int rs = decode_huff(br, ac[c.ta]);
-        int r = rs >> 4, s = rs & 15;
-        if (s == 0) {
-          if (r < 15) {
-            eobrun = (1 << r) - 1;
-            if (r) eobrun += br.read_bits(r);
-            break;
-          }
-          k += 16;  // ZRL
-          continue;
-        }
-        k += r;
-        if (k > 63) break;
-        blk[k] = extend(br.read_bits(s), s) << Al;
-        ++k;
-      }
-    } else {  // AC refinement (G.2.3 / jpeg6b decode_mcu_AC_refine)
-      int p1 = 1 << Al, m1 = (-1) << Al;
-      int k = Ss;
-      if (eobrun == 0) {
-        for (; k <= Se; ) {
-          int rs = decode_huff(br, ac[c.ta]);
-          int r = rs >> 4, s = rs & 15;
-          int val = 0;
-          if (s == 0) {
-            if (r < 15) {
-              eobrun = (1 << r);
-              if (r) eobrun += br.read_bits(r);
-              break;  // EOB logic handled below
-            }
-            // ZRL: skip 16 zero-history coefficients
-          } else {
-            val = br.read_bit() ? p1 : m1;
-          }
-          while (k <= Se) {
-            int32_t& co = blk[k];
-            if (co != 0) {
-              if (br.read_bit() && (co & p1) == 0)
-                co += (co >= 0) ? p1 : m1;
-            } else {
-              if (r == 0) {
-                if (val) blk[k] = val;
-                ++k;
-                break;
-              }
-              --r;
-            }
-            ++k;
-          }
-        }
-      }
-      if (eobrun > 0) {
-        // append correction bits to remaining nonzero coefficients
-        for (; k <= Se; ++k) {
-          int32_t& co = blk[k];
-          if (co != 0) {
-            if (br.read_bit() && (co & p1) == 0)
-              co += (co >= 0) ? p1 : m1;
-          }
-        }
-        --eobrun;
-      }
-    }
-  }
-};
 
 // orthonormal 8-point DCT-III basis (matches scipy idctn(norm="ortho"))
 struct IdctBasis {
@@ -422,8 +68,7 @@ torch::Tensor decode_jpeg_native(py::bytes data_b) {
 
   Decoder dec(data, n);
   dec.parse();
-  if (dec.W <= 0 || dec.H <= 0 || dec.comps.empty())
-    throw std::runtime_error("no frame decoded");
+  dec.check_reconstructible();
 
   const int W = dec.W, H = dec.H;
   const int nc = (int)dec.comps.size();
@@ -485,7 +130,36 @@ torch::Tensor decode_jpeg_native(py::bytes data_b) {
   return out;
 }
 
+// Entropy decode only: the coefficient store in the layout the device
+// reconstruction (ops/hip/image_kernels.hip) reads.  Returns
+// (coef int16 (blocks, 64) zigzag, qt uint16 (4, 64) zigzag, W, H,
+//  [(h, v, tq, bw, bh, block_off) per component]).
+py::tuple decode_jpeg_coefficients(py::bytes data_b) {
+  std::string s = data_b;
+  Exported ex;
+  torch::Tensor coef, qt;
+  {
+    py::gil_scoped_release nogil;
+    Decoder dec((const uint8_t*)s.data(), s.size());
+    dec.parse();
+    export_coefficients(dec, ex);
+    coef = torch::empty({(int64_t)ex.blocks, 64}, torch::kInt16);
+    std::memcpy(coef.data_ptr<int16_t>(), ex.coef.data(),
+                ex.coef.size() * sizeof(int16_t));
+    qt = torch::empty({4, 64}, torch::kUInt16);
+    std::memcpy(qt.data_ptr(), ex.qt, sizeof(ex.qt));
+  }
+  py::list comps;
+  for (int ci = 0; ci < ex.nc; ++ci) {
+    const CompGeom& g = ex.comp[ci];
+    comps.append(py::make_tuple(g.h, g.v, g.tq, g.bw, g.bh, g.block_off));
+  }
+  return py::make_tuple(coef, qt, ex.W, ex.H, comps);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_jpeg", &decode_jpeg_native,
         "native JPEG decode (baseline + progressive) -> uint8 HxW[x3]");
+  m.def("decode_jpeg_coefficients", &decode_jpeg_coefficients,
+        "entropy decode only -> (coef int16, qt uint16, W, H, components)");
 }

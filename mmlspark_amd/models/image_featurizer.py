@@ -79,6 +79,42 @@ def _rows_to_batch(vals, size: int) -> torch.Tensor:
     return batch
 
 
+_UNIT_LUT = {}
+
+
+def _unit_lut(device) -> torch.Tensor:
+    """k / 255 for k = 0..255, divided on the host by the op _rows_to_batch
+    uses and then moved: a device-side scalar divide multiplies by a
+    reciprocal and lands an ulp away on many values."""
+    key = str(device)
+    if key not in _UNIT_LUT:
+        _UNIT_LUT[key] = torch.arange(256, dtype=torch.float32).div_(
+            255.0).to(device)
+    return _UNIT_LUT[key]
+
+
+def _jpeg_rows_to_device_batch(vals, size: int, device) -> torch.Tensor:
+    """JPEG byte cells -> (N,3,size,size) f32 on `device`: decode with
+    io_http.jpeg_device, then the same stack / permute / float ÷ 255 /
+    bilinear resize as _rows_to_batch, as torch ops on the device."""
+    from ..io_http.jpeg_device import decode_jpeg_batch
+    imgs = decode_jpeg_batch([bytes(v) for v in vals], device)
+    imgs = [t.unsqueeze(2).expand(-1, -1, 3) if t.ndim == 2 else t
+            for t in imgs]
+    lut = _unit_lut(device)
+
+    def to_unit_nchw(t):  # (N,H,W,3) uint8 -> (N,3,H,W) f32 in [0, 1]
+        b = lut[t.permute(0, 3, 1, 2).int()]
+        if b.shape[-1] != size or b.shape[-2] != size:
+            b = torch.nn.functional.interpolate(
+                b, size=(size, size), mode="bilinear", align_corners=False)
+        return b
+
+    if all(t.shape == imgs[0].shape for t in imgs):
+        return to_unit_nchw(torch.stack(imgs))
+    return torch.cat([to_unit_nchw(t.unsqueeze(0)) for t in imgs])
+
+
 @register
 class TorchModel(Model):
     """Generic batched torch-module inference transformer (CNTKModel analog).
@@ -160,6 +196,10 @@ class ImageFeaturizer(TorchModel):
     modelPath = Param("modelPath", "optional state-dict path", None)
     inputCol = Param("inputCol", "image column", "image")
     outputCol = Param("outputCol", "feature vector column", "features")
+    decodeOnDevice = Param("decodeOnDevice",
+                           "decode JPEG byte cells on the GPU (host Huffman "
+                           "decode, device dequant/IDCT/colour) when the "
+                           "stage runs on a CUDA device", False, toBool)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -182,7 +222,20 @@ class ImageFeaturizer(TorchModel):
         return self.module(batch, cut_output_layers=self.get("cutOutputLayers"))
 
     def _coerce(self, vals):
-        return _rows_to_batch(vals, self.get("imageSize"))
+        size = self.get("imageSize")
+        if self.get("decodeOnDevice") and len(vals):
+            device = default_device(self.get("device"))
+            if device.type == "cuda" and all(
+                    isinstance(v, (bytes, bytearray, memoryview))
+                    and bytes(v[:2]) == b"\xff\xd8" for v in vals):
+                try:
+                    return _jpeg_rows_to_device_batch(vals, size, device)
+                except ValueError:
+                    # a stream the device path rejects: this batch takes the
+                    # host path below (a missing kernel is not a ValueError
+                    # and is not swallowed)
+                    pass
+        return _rows_to_batch(vals, size)
 
 
 @register

@@ -238,3 +238,105 @@ def predict_leaf_csr(node_feature, node_threshold, node_left, node_right,
     return cpu_ref.predict_leaf_csr(
         node_feature, node_threshold, node_left, node_right, node_leaf_index,
         tree_offsets, indptr, col, val, n_cols, cat_offset, cat_words)
+
+
+# ------------------------------------------------------------------- images
+JPEG_MAX_PIXELS = 1 << 26
+
+
+def jpeg_work_items(W, H, hmax, vmax):
+    """Work items (workgroups) jpeg_reconstruct_k spends on one image: a run
+    of G = max(1, 4 // (hmax*vmax)) MCUs each.  Works on ints and arrays."""
+    mcux = (W + 8 * hmax - 1) // (8 * hmax)
+    mcuy = (H + 8 * vmax - 1) // (8 * vmax)
+    G = 4 // (hmax * vmax)
+    G = G + (G < 1)
+    return ((mcux + G - 1) // G) * mcuy
+
+
+def check_jpeg_descriptors(n_blocks, qt, img_desc, comp_desc, work_off,
+                           out_bytes):
+    """Validate a batch's descriptors against the buffer sizes — everything
+    jpeg_reconstruct_k indexes with.  O(N) on CPU tensors; raises ValueError
+    and nothing is launched.  Runs before the GPU launch and before the CPU
+    reference alike."""
+    import numpy as np
+
+    def bad(msg):
+        raise ValueError("jpeg_reconstruct: " + msg)
+
+    for name, t in (("img_desc", img_desc), ("comp_desc", comp_desc),
+                    ("work_off", work_off)):
+        if t.is_cuda or t.dtype != torch.int64:
+            bad(name + " must be a CPU int64 tensor")
+    n = img_desc.shape[0] if img_desc.dim() == 2 else -1
+    if (n < 0 or tuple(img_desc.shape) != (n, 4)
+            or tuple(comp_desc.shape) != (n, 3, 4)
+            or tuple(work_off.shape) != (n + 1,)
+            or tuple(qt.shape) != (n, 4, 64)):
+        bad("descriptor shapes do not agree on the batch size")
+    if n == 0:
+        return
+    d = img_desc.numpy()
+    cd = comp_desc.numpy()
+    wo = work_off.numpy()
+    W, H, nc, out_off = d[:, 0], d[:, 1], d[:, 2], d[:, 3]
+    if ((W < 1) | (H < 1) | (W > 65535) | (H > 65535)).any() \
+            or (W * H > JPEG_MAX_PIXELS).any():
+        bad("image size out of range")
+    if (~np.isin(nc, (1, 3))).any():
+        bad("component count must be 1 or 3")
+    hmax, vmax = cd[:, 0, 0], cd[:, 0, 1]
+    if ((hmax < 1) | (hmax > 4) | (vmax < 1) | (vmax > 4)).any():
+        bad("sampling factor out of range")
+    mcux = (W + 8 * hmax - 1) // (8 * hmax)
+    mcuy = (H + 8 * vmax - 1) // (8 * vmax)
+    for c in range(3):
+        used = nc > c
+        h, v, tq, off = (np.where(used, cd[:, c, k], (1, 1, 0, 0)[k])
+                         for k in range(4))
+        if ((h < 1) | (h > 4) | (v < 1) | (v > 4)).any():
+            bad("sampling factor out of range")
+        if ((hmax % h != 0) | (vmax % v != 0)).any():
+            bad("sampling factor does not divide component 0's")
+        if ((tq < 0) | (tq > 3)).any():
+            bad("quantisation table id above 3")
+        if ((off < 0) | (off + mcux * h * mcuy * v > n_blocks))[used].any():
+            bad("component blocks run past the coefficient buffer")
+    if ((out_off < 0) | (out_off + H * W * nc > out_bytes)).any():
+        bad("image pixels run past the output buffer")
+    items = jpeg_work_items(W, H, hmax, vmax)
+    if wo[0] != 0 or (np.diff(wo) != items).any():
+        bad("work_off is not the prefix sum of the per-image work items")
+    if wo[-1] >= (1 << 31):
+        bad("batch too large for one launch")
+
+
+def jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off, out):
+    """Reconstruct a batch of entropy-decoded JPEGs into the uint8 buffer
+    `out` (dequant, IDCT, chroma replication, YCbCr->RGB, crop) in one
+    launch.  coef (blocks, 64) int16 and qt (N, 4, 64) uint16 live where
+    `out` lives; the three descriptor tensors (layout in image_kernels.hip)
+    are CPU int64: they are checked against the buffer sizes here, then
+    copied to the device.  Pin them to make that copy asynchronous."""
+    if coef.dim() != 2 or coef.shape[1] != 64 or coef.dtype != torch.int16 \
+            or qt.dtype != torch.uint16 or out.dtype != torch.uint8 \
+            or out.dim() != 1:
+        raise ValueError("jpeg_reconstruct: coef must be (blocks, 64) int16, "
+                         "qt uint16 and out a flat uint8 buffer")
+    if coef.device != out.device or qt.device != out.device:
+        raise ValueError("jpeg_reconstruct: coef, qt and out must share a "
+                         "device")
+    check_jpeg_descriptors(coef.shape[0], qt, img_desc, comp_desc, work_off,
+                           out.numel())
+    if out.is_cuda:
+        ext = _require_ext()
+        dev = out.device
+        ext.jpeg_reconstruct(
+            coef.contiguous(), qt.contiguous(),
+            img_desc.to(dev, non_blocking=True),
+            comp_desc.to(dev, non_blocking=True),
+            work_off.to(dev, non_blocking=True), int(work_off[-1]), out)
+        return out
+    return cpu_ref.jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off,
+                                    out)

@@ -309,3 +309,78 @@ def csr_gather_bins(indptr, col, binv, rows, feature: int, zero_bin: int):
         m = col[e].long() == int(feature)
         out[rpos[m]] = binv[e[m]].long()
     return out
+
+
+# ------------------------------------------------------------------- images
+_JPEG_ZIGZAG = (
+    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5,
+    12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+    58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+
+
+def _jpeg_idct_basis() -> torch.Tensor:
+    """Orthonormal DCT-III basis b[x, u], computed like the host decoder."""
+    import math
+    b = torch.empty(8, 8, dtype=torch.float64)
+    for x in range(8):
+        for u in range(8):
+            a = math.sqrt(1.0 / 8.0) if u == 0 else math.sqrt(2.0 / 8.0)
+            b[x, u] = a * math.cos((2 * x + 1) * u * math.pi / 16.0)
+    return b
+
+
+def _jpeg_plane(coef, q, bw: int, bh: int, basis) -> torch.Tensor:
+    """(bw*bh, 64) zigzag int16 blocks -> (bh*8, bw*8) f32 samples.  Every
+    product and sum is its own rounded f64 operation, added in the host
+    decoder's order (u = 0..7, then v = 0..7), so the result is the host's."""
+    zz = torch.tensor(_JPEG_ZIGZAG, dtype=torch.long)
+    dq = torch.zeros(coef.shape[0], 64, dtype=torch.float64)
+    dq[:, zz] = coef.double() * q.double()
+    dq = dq.view(-1, 8, 8)                       # [block, y, u]
+    tmp = torch.zeros_like(dq)                   # [block, y, x]
+    for u in range(8):
+        tmp = tmp + basis[:, u].view(1, 1, 8) * dq[:, :, u].unsqueeze(2)
+    px = torch.zeros_like(dq)                    # [block, y, x]
+    for v in range(8):
+        px = px + basis[:, v].view(1, 8, 1) * tmp[:, v, :].unsqueeze(1)
+    px = (px + 128.0).float()
+    return px.view(bh, bw, 8, 8).permute(0, 2, 1, 3).reshape(bh * 8, bw * 8)
+
+
+def _jpeg_u8(v: torch.Tensor) -> torch.Tensor:
+    return (v + 0.5).clamp(0.0, 255.0).to(torch.uint8)
+
+
+def jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off, out):
+    """Dequantise, IDCT, replicate chroma, convert and crop a batch of
+    entropy-decoded JPEGs into `out` — matches jpeg_reconstruct_k and the
+    host decoder.  Descriptor layout as in image_kernels.hip; work_off is
+    the kernel's scheduling table and is not needed here."""
+    basis = _jpeg_idct_basis()
+    qt = qt.to(torch.int32)
+    for i in range(img_desc.shape[0]):
+        W, H, nc, out_off = (int(t) for t in img_desc[i])
+        hmax, vmax = int(comp_desc[i, 0, 0]), int(comp_desc[i, 0, 1])
+        mcux = (W + 8 * hmax - 1) // (8 * hmax)
+        mcuy = (H + 8 * vmax - 1) // (8 * vmax)
+        planes = []
+        for c in range(nc):
+            h, v, tq, off = (int(t) for t in comp_desc[i, c])
+            bw, bh = mcux * h, mcuy * v
+            planes.append((_jpeg_plane(coef[off:off + bw * bh], qt[i, tq],
+                                       bw, bh, basis), h, v))
+        if nc == 1:
+            img = _jpeg_u8(planes[0][0][:H, :W])
+        else:
+            ys, xs = torch.arange(H), torch.arange(W)
+            Y = planes[0][0][:H, :W]
+            Cb, Cr = (p[(ys // (vmax // v)).unsqueeze(1),
+                        (xs // (hmax // h)).unsqueeze(0)] - 128.0
+                      for p, h, v in planes[1:])
+            r = Y + 1.402 * Cr
+            g = Y - 0.344136 * Cb - 0.714136 * Cr
+            b = Y + 1.772 * Cb
+            img = torch.stack([_jpeg_u8(r), _jpeg_u8(g), _jpeg_u8(b)], dim=2)
+        out[out_off:out_off + img.numel()] = img.reshape(-1)
+    return out

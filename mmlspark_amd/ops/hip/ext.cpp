@@ -66,6 +66,9 @@ void launch_csr_hist_fixed_lds(const long*, const int*, const unsigned char*,
 void launch_csr_partition(const long*, const int*, const unsigned char*,
                           const int*, long, int, int, int, const unsigned*,
                           unsigned char*, int*, int*, int*, hipStream_t);
+void launch_jpeg_reconstruct(const short*, const unsigned short*, const long*,
+                             const long*, const long*, int, long,
+                             unsigned char*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -482,6 +485,46 @@ std::tuple<torch::Tensor, torch::Tensor> csr_partition_rows(
   return {out.slice(0, 0, nl), out.slice(0, nl, m)};
 }
 
+// ------------------------------------------------------------------- images
+// JPEG reconstruction (dequant + IDCT + colour + crop) of a whole batch in
+// one launch, written into `out` in place.  The descriptors must already
+// have passed ops/backend.py::check_jpeg_descriptors — this only checks that
+// the tensors are what the kernel's pointer types say they are.
+void jpeg_reconstruct(torch::Tensor coef, torch::Tensor qt,
+                      torch::Tensor img_desc, torch::Tensor comp_desc,
+                      torch::Tensor work_off, long n_items,
+                      torch::Tensor out) {
+  CHECK_DEV(coef); CHECK_CONTIG(coef);
+  CHECK_DEV(qt); CHECK_CONTIG(qt);
+  CHECK_DEV(img_desc); CHECK_CONTIG(img_desc);
+  CHECK_DEV(comp_desc); CHECK_CONTIG(comp_desc);
+  CHECK_DEV(work_off); CHECK_CONTIG(work_off);
+  CHECK_DEV(out); CHECK_CONTIG(out);
+  TORCH_CHECK(coef.dtype() == torch::kInt16, "coef must be int16");
+  TORCH_CHECK(qt.dtype() == torch::kUInt16, "qt must be uint16");
+  TORCH_CHECK(img_desc.dtype() == torch::kInt64 &&
+              comp_desc.dtype() == torch::kInt64 &&
+              work_off.dtype() == torch::kInt64,
+              "descriptors must be int64");
+  TORCH_CHECK(out.dtype() == torch::kUInt8, "out must be uint8");
+  const long n_img = img_desc.size(0);
+  TORCH_CHECK(img_desc.numel() == n_img * 4 &&
+              comp_desc.numel() == n_img * 12 &&
+              work_off.numel() == n_img + 1 &&
+              qt.numel() == n_img * 4 * 64,
+              "descriptor shapes do not agree on the batch size");
+  TORCH_CHECK(n_img < (1L << 31) && n_items >= 0 && n_items < (1L << 31),
+              "batch too large for one launch");
+  TORCH_CHECK(((uintptr_t)out.data_ptr() & 3) == 0,
+              "out must be 4-byte aligned");
+  if (n_img == 0 || n_items == 0) return;
+  launch_jpeg_reconstruct(
+      (const short*)coef.data_ptr<int16_t>(),
+      (const unsigned short*)qt.data_ptr(), img_desc.data_ptr<long>(),
+      comp_desc.data_ptr<long>(), work_off.data_ptr<long>(), (int)n_img,
+      n_items, out.data_ptr<uint8_t>(), cur_stream());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -509,4 +552,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused CSR leaf partition (binary-search predicate, single sync)");
   m.def("csr_hist_fixed_tot", &csr_hist_fixed_tot,
         "wave-cooperative CSR histogram + in-kernel leaf totals");
+  m.def("jpeg_reconstruct", &jpeg_reconstruct,
+        "batched JPEG dequant + IDCT + colour conversion into a uint8 buffer");
 }

@@ -18,7 +18,8 @@ HIP_DIR = os.path.join(ROOT, "mmlspark_amd", "ops", "hip")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 
-KERNEL_SOURCES = ["gbdt_kernels.hip", "vw_kernels.hip"]
+KERNEL_SOURCES = ["gbdt_kernels.hip", "vw_kernels.hip",
+                  "image_kernels.hip"]
 
 
 def compile_hip_kernels():
@@ -70,6 +71,8 @@ setup(
             name="mmlspark_amd.io_http._jpeg_native",
             sources=[os.path.join(ROOT, "mmlspark_amd", "io_http",
                                   "jpeg_native.cpp")],
+            depends=[os.path.join(ROOT, "mmlspark_amd", "io_http",
+                                  "jpeg_parse.h")],
             extra_compile_args=["-O3"],
         ),
     ],
