@@ -41,13 +41,24 @@ __device__ __forceinline__ float invariant_dp(int loss, float pred, float y,
       return (y - pred) * (-expm1f(-h_eta));
     case 1: {  // logistic: q=y*p obeys e^q + q = e^{q0}+q0+h_eta
       const float q0 = y * pred;
+      // A = e^{q0} >= e^30: the linear term is below float resolution
       if (q0 > 30.0f) return y * (h_eta * __expf(-q0));
-      const float A = __expf(q0);
-      float d = log1pf(h_eta / (A + 1.0f));
+      // d = q-q0 >= 0 is the root of g(d) = A*expm1(d) + d - h_eta, convex
+      // and increasing, so Newton started at or right of the root descends
+      // onto it and never passes it.  Both h_eta (g = A*expm1) and
+      // log1p(h_eta/A) (g = d) are right of it; the smaller is within a few
+      // steps of it for every (q0, h_eta).  Where A underflows,
+      // log1p(h_eta/A) = log(h_eta) - q0.
+      const float start = q0 > -40.0f ? log1pf(h_eta / expf(q0))
+                                      : logf(h_eta) - q0;
+      float d = fminf(h_eta, fmaxf(start, 0.0f));
 #pragma unroll
-      for (int it = 0; it < 8; ++it) {  // Newton on convex A*expm1(d)+d-h_eta
-        const float g = A * expm1f(d) + d - h_eta;
-        d = fmaxf(d - g / (A * __expf(d) + 1.0f), 0.0f);
+      for (int it = 0; it < 8; ++it) {
+        // A*e^d as e^{q0+d} (<= A + h_eta: no overflow) and A*expm1(d) as
+        // that times (1 - e^{-d}): finite for every q0 and d
+        const float E = expf(q0 + d);
+        const float g = E * (-expm1f(-d)) + d - h_eta;
+        d = fmaxf(d - g / (E + 1.0f), 0.0f);
       }
       return y * d;
     }
