@@ -23,18 +23,28 @@
 //    Candidate order is deterministic across ranks, so the histogram
 //    all_reduce order matches and speculation is safe in multi-rank mode.
 //
+//  * STREAM POOL: on a single rank the (up to three) chains in flight go
+//    round-robin over the caller's stream and up to two pooled side streams
+//    (MMLSPARK_AMD_GROWER_STREAMS, 1-3), so one leaf's LDS-atomic-bound
+//    histogram can run next to another leaf's HBM-bound scatter.  Chains of
+//    different leaves touch disjoint arena ranges and each has its own
+//    counters, so they need no ordering among themselves.
+//
 // Categorical features fall back to the Python grower (models/gbdt/
 // trainer.py).  Replaces the growth loop the reference delegates to
 // LightGBM's serial_tree_learner behind LGBM_BoosterUpdateOneIter
 // (SURVEY §2.1).
 #include <torch/extension.h>
 #include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
+#include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <memory>
+#include <mutex>
 #include <numeric>
 #include <queue>
 #include <vector>
@@ -48,7 +58,7 @@ void launch_partition_arena(const void*, const void*, const int*, void*,
                             const unsigned*, int*, int*, long, int,
                             hipStream_t);
 void launch_hist_pair_range(const void*, const void*, long, long, long,
-                            long long*, int, int, int, const int*, int,
+                            long long*, int, int, int, const int*, int, long,
                             hipStream_t);
 void launch_sibling_scan(const long long*, const long long*, long long*, int,
                          long, int, float, float, float, float, long,
@@ -62,6 +72,41 @@ static hipStream_t grower_stream() {
 }
 
 namespace {
+
+constexpr int kMaxGrowerStreams = 3;
+// default of MMLSPARK_AMD_GROWER_STREAMS (docs/benchmarks.md, stream sweep)
+constexpr int kDefaultGrowerStreams = 3;
+
+// Streams a tree's chains rotate over: [0] is the caller's stream, the rest
+// come from torch's stream pool ONCE per process and device, so every tree
+// reuses the same two side streams and, with the caller's, the grower never
+// holds more than three (the runtime's default is four hardware queues).
+std::vector<c10::hip::HIPStream> grower_streams(int n) {
+  auto cur = c10::hip::getCurrentHIPStream();
+  std::vector<c10::hip::HIPStream> out{cur};
+  if (n <= 1) return out;
+  static std::mutex mu;
+  static std::vector<std::vector<c10::hip::HIPStream>> side;  // per device
+  std::lock_guard<std::mutex> lock(mu);
+  const size_t dev = (size_t)cur.device_index();
+  if (side.size() <= dev) side.resize(dev + 1);
+  while ((int)side[dev].size() < kMaxGrowerStreams - 1)
+    side[dev].push_back(
+        c10::hip::getStreamFromPool(false, cur.device_index()));
+  for (int i = 0; i + 1 < n; ++i) out.push_back(side[dev][i]);
+  return out;
+}
+
+int grower_streams_from_env() {
+  const char* e = std::getenv("MMLSPARK_AMD_GROWER_STREAMS");
+  if (!e || !*e) return kDefaultGrowerStreams;
+  char* end = nullptr;
+  const long v = std::strtol(e, &end, 10);
+  TORCH_CHECK(*end == '\0' && v >= 1 && v <= kMaxGrowerStreams,
+              "MMLSPARK_AMD_GROWER_STREAMS must be 1..", kMaxGrowerStreams,
+              ", got '", e, "'");
+  return (int)v;
+}
 
 struct GrowCtx {
   long n_arena;    // rows in the arena (= rows_root size after bagging)
@@ -90,8 +135,13 @@ struct GrowCtx {
   std::vector<int> cat_feats;
   double cat_smooth = 10.0;
   torch::Tensor cat_idx_dev;  // i64 device indices for index_select
-  torch::Tensor scratch;    // partition block counters (stream-ordered reuse)
-  torch::Tensor total;      // partition left-count (stream-ordered reuse)
+  // chains rotate over these streams; [0] is the caller's.  The partition
+  // block counters and left count are reused in stream order, so every
+  // stream has its own pair.
+  std::vector<c10::hip::HIPStream> streams;
+  size_t next_stream = 0;
+  torch::Tensor scratch[kMaxGrowerStreams];
+  torch::Tensor total[kMaxGrowerStreams];
   // per-tree histogram slabs, one slot per split: small children accumulate
   // into pre-zeroed slots, big children are written whole by the sibling scan
   torch::Tensor slab_zero, slab_raw;
@@ -108,8 +158,15 @@ struct SplitJob {
   long nl_known = -1;       // host-known left count (single-rank fast path)
   hipEvent_t ev = nullptr;
 
+  // A job that was speculated but never committed may still be in flight:
+  // its pinned buffers are targets of raw hipMemcpyAsync calls the host
+  // allocator knows nothing about, so they must outlive the chain.  For a
+  // consumed job the event is long complete and this returns at once.
   ~SplitJob() {
-    if (ev) (void)hipEventDestroy(ev);
+    if (ev) {
+      (void)hipEventSynchronize(ev);
+      (void)hipEventDestroy(ev);
+    }
   }
 };
 
@@ -156,7 +213,7 @@ torch::Tensor build_hist(GrowCtx& ctx, int buf, long lo, long m,
   launch_hist_pair_range(
       ctx.pair[buf].data_ptr(), ctx.ghq[buf].data_ptr(), ctx.n_arena, lo, m,
       (long long*)hist.data_ptr<int64_t>(), ctx.n_bins, ctx.npairs,
-      ctx.tail_bytes, nl_dev, side, grower_stream());
+      ctx.tail_bytes, nl_dev, side, 0, grower_stream());
   if (ctx.has_reduce) {
     std::vector<at::Tensor> v{hist};
     ctx.pg->allreduce(v)->wait();  // stream-ordered on RCCL; no GIL
@@ -312,7 +369,20 @@ void resolve_best(const GrowCtx& ctx, SplitJob& job, int hi, LeafCand& c) {
   }
 }
 
+// Launch a leaf's whole chain (bitset copy, count, scatter, small-child
+// histogram, sibling scan, readbacks, event) on the next stream of the pool.
+// No device-side wait orders it after other chains, and none is needed: a
+// chain is launched only for a leaf whose creating chain's event the host
+// has already waited on (the root: the root scan's event, which also covers
+// the arena setup), and live leaves own disjoint arena ranges.  Keep that
+// invariant when changing the loop below.
 void launch_job(GrowCtx& ctx, LeafCand& leaf) {
+  const size_t si = ctx.next_stream;
+  ctx.next_stream = (ctx.next_stream + 1) % ctx.streams.size();
+  // grower_stream() and every tensor allocated below belong to this stream
+  c10::hip::HIPStreamGuard guard(ctx.streams[si]);
+  int* const scratch = ctx.scratch[si].data_ptr<int>();
+  int* const total = ctx.total[si].data_ptr<int>();
   auto job = std::make_shared<SplitJob>();
   const long m = leaf.hi - leaf.lo;
   const int src = leaf.buf, dst = leaf.buf ^ 1;
@@ -337,8 +407,7 @@ void launch_job(GrowCtx& ctx, LeafCand& leaf) {
       ctx.rowid[src].data_ptr<int>(), ctx.pair[dst].data_ptr(),
       ctx.ghq[dst].data_ptr(), ctx.rowid[dst].data_ptr<int>(), ctx.n_arena,
       ctx.npairs, leaf.lo, m, leaf.feat, leaf.bin, cat_bits,
-      ctx.scratch.data_ptr<int>(), ctx.total.data_ptr<int>(), 0, 0,
-      grower_stream());
+      scratch, total, 0, 0, grower_stream());
 
   const double CL = leaf.CL, CR = leaf.C - leaf.CL;
   const bool left_small = CL <= CR;  // by GLOBAL counts: same on all ranks
@@ -349,13 +418,11 @@ void launch_job(GrowCtx& ctx, LeafCand& leaf) {
     const long m_s = left_small ? job->nl_known : m - job->nl_known;
     hist_small = build_hist(ctx, dst, lo_s, m_s);
   } else {
-    hist_small = build_hist(ctx, dst, leaf.lo, m,
-                            ctx.total.data_ptr<int>(), left_small ? 0 : 1);
+    hist_small = build_hist(ctx, dst, leaf.lo, m, total, left_small ? 0 : 1);
     job->nl_host = torch::empty({1}, torch::TensorOptions()
                                          .dtype(torch::kInt32)
                                          .pinned_memory(true));
-    (void)hipMemcpyAsync(job->nl_host.data_ptr<int>(),
-                         ctx.total.data_ptr<int>(), sizeof(int),
+    (void)hipMemcpyAsync(job->nl_host.data_ptr<int>(), total, sizeof(int),
                          hipMemcpyDeviceToHost, grower_stream());
   }
   auto hist_big = hist_slot(ctx, false);
@@ -424,11 +491,17 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
   }
   ctx.has_reduce = ctx.pg && ctx.pg->getSize() > 1;
   ctx.distributed = distributed;
+  // a real process group stays on one stream: the order of collectives
+  // across streams would have to match on every rank
+  ctx.streams = grower_streams(ctx.has_reduce ? 1 : grower_streams_from_env());
 
   py::gil_scoped_release nogil;
 
-  ctx.scratch = torch::empty({4096}, rows_root.options().dtype(torch::kInt32));
-  ctx.total = torch::zeros({1}, rows_root.options().dtype(torch::kInt32));
+  for (size_t s = 0; s < ctx.streams.size(); ++s) {
+    ctx.scratch[s] =
+        torch::empty({4096}, rows_root.options().dtype(torch::kInt32));
+    ctx.total[s] = torch::zeros({1}, rows_root.options().dtype(torch::kInt32));
+  }
   auto i64d = rows_root.options().dtype(torch::kInt64);
   // one zero fill per tree instead of one per split: root + one small child
   // per split, with room for the two speculated chains
@@ -570,6 +643,18 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
     n_leaves += 1;
   }
 
+  // The caller's stream joins every side stream before it reads the row-id
+  // segments and before the arena, the slabs and the counters (all allocated
+  // on the caller's stream) are released: chains that were speculated but
+  // never committed may still be writing them.
+  for (size_t s = 1; s < ctx.streams.size(); ++s) {
+    hipEvent_t ev = nullptr;
+    (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    (void)hipEventRecord(ev, ctx.streams[s].stream());
+    (void)hipStreamWaitEvent(grower_stream(), ev, 0);
+    (void)hipEventDestroy(ev);
+  }
+
   // leaf ordinals in node order; collect original-row-id segments from each
   // leaf's own arena buffer
   std::sort(finals.begin(), finals.end(),
@@ -695,6 +780,47 @@ torch::Tensor partition_arena(torch::Tensor pair_src, torch::Tensor ghq_src,
   return total;
 }
 
+// Test/tuning entry for the range-mode histogram: adds the (g, h, count)
+// sums of arena rows [lo, lo+m) into `hist` (nf_pad, n_bins, 3).  With side
+// 0 / 1 only the left / right part of the range is read, split at the device
+// count nl_dev[0], which the caller keeps within [0, m], as it keeps every
+// bin byte of the valid features below n_bins: neither can be checked here
+// without reading the arena back.  chunk = 0 takes the launcher's own policy.
+void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
+                     torch::Tensor hist, long n_bins, long tail_bytes,
+                     c10::optional<torch::Tensor> nl_dev, long side,
+                     long chunk) {
+  TORCH_CHECK(pair.is_cuda() && pair.is_contiguous() && pair.dim() == 2 &&
+              pair.scalar_type() == torch::kInt64,
+              "pair planes: contiguous (npairs, n_arena) i64");
+  const long n_arena = pair.size(1);
+  const long npairs = pair.size(0);
+  TORCH_CHECK(ghq.is_cuda() && ghq.is_contiguous() &&
+              ghq.scalar_type() == torch::kInt64 &&
+              ghq.numel() == 2 * n_arena,
+              "ghq: contiguous (n_arena, 2) i64");
+  TORCH_CHECK(lo >= 0 && m >= 0 && lo + m <= n_arena, "range out of bounds");
+  TORCH_CHECK(n_bins >= 1 && n_bins <= 256, "n_bins must be 1..256");
+  TORCH_CHECK(tail_bytes >= 1 && tail_bytes <= 8, "tail_bytes must be 1..8");
+  TORCH_CHECK(hist.is_cuda() && hist.is_contiguous() &&
+              hist.scalar_type() == torch::kInt64 &&
+              hist.numel() == npairs * 8 * n_bins * 3,
+              "hist: contiguous (npairs * 8, n_bins, 3) i64");
+  TORCH_CHECK(side >= -1 && side <= 1, "side must be -1, 0 or 1");
+  TORCH_CHECK(chunk >= 0, "chunk must be >= 0");
+  const int* nl = nullptr;
+  if (side >= 0) {
+    TORCH_CHECK(nl_dev.has_value() && nl_dev->is_cuda() &&
+                nl_dev->scalar_type() == torch::kInt32 &&
+                nl_dev->numel() == 1, "nl_dev: (1,) i32 device");
+    nl = nl_dev->data_ptr<int>();
+  }
+  launch_hist_pair_range(pair.data_ptr(), ghq.data_ptr(), n_arena, lo, m,
+                         (long long*)hist.data_ptr<int64_t>(), (int)n_bins,
+                         (int)npairs, (int)tail_bytes, nl, (int)side, chunk,
+                         grower_stream());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grow_tree_native", &grow_tree_native,
         "native leaf-wise GBDT tree growth (numeric features, arena mode)");
@@ -706,6 +832,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ghq_dst"), py::arg("rowid_dst"), py::arg("lo"), py::arg("m"),
         py::arg("feature"), py::arg("thr"), py::arg("cat_bits") = py::none(),
         py::arg("chunk") = 0, py::arg("plane_groups") = 0);
+  m.def("hist_pair_range", &hist_pair_range,
+        "range-mode arena histogram, accumulated into hist", py::arg("pair"),
+        py::arg("ghq"), py::arg("lo"), py::arg("m"), py::arg("hist"),
+        py::arg("n_bins"), py::arg("tail_bytes"),
+        py::arg("nl_dev") = py::none(), py::arg("side") = -1,
+        py::arg("chunk") = 0);
   m.def("allreduce_native", &allreduce_native,
         "GIL-free c10d all_reduce through the same C++ path as the grower");
 }

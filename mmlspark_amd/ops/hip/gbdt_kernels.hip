@@ -814,6 +814,12 @@ __global__ void hist_pair_range_k(
   if ((long)blockIdx.x * chunk >= m_eff) return;
   extern __shared__ unsigned long long lds64[];
   const int tid = threadIdx.x;
+  // two LDS planes at 8-byte stride: all g cells, then all cnt|h cells.
+  // Interleaved [g][cnt|h] cells at 16-byte stride put every g atomic of a
+  // wave on one half of the bank pairs and every h atomic on the other;
+  // measured 1068 -> 847 us at 10M rows, 31.0 -> 27.6 us at 2^16
+  // (docs/benchmarks.md)
+  const int hplane = 8 * n_bins;
   const int lds_elems = 8 * n_bins * 2;
   for (int i = tid; i < lds_elems; i += blockDim.x) lds64[i] = 0ull;
   __syncthreads();
@@ -841,9 +847,9 @@ __global__ void hist_pair_range_k(
       for (int j = 0; j < 8; ++j) {
         if (j >= jmax) break;
         const int b = (int)((v[u] >> (8 * j)) & 0xffull);
-        unsigned long long* cell = &lds64[(j * n_bins + b) * 2];
-        atomicAdd(cell + 0, (unsigned long long)q[u].x);
-        atomicAdd(cell + 1, (unsigned long long)q[u].y);
+        unsigned long long* cell = &lds64[j * n_bins + b];
+        atomicAdd(cell, (unsigned long long)q[u].x);
+        atomicAdd(cell + hplane, (unsigned long long)q[u].y);
       }
     }
   }
@@ -854,9 +860,9 @@ __global__ void hist_pair_range_k(
     for (int j = 0; j < 8; ++j) {
       if (j >= jmax) break;
       const int b = (int)((v >> (8 * j)) & 0xffull);
-      unsigned long long* cell = &lds64[(j * n_bins + b) * 2];
-      atomicAdd(cell + 0, (unsigned long long)q.x);
-      atomicAdd(cell + 1, (unsigned long long)q.y);
+      unsigned long long* cell = &lds64[j * n_bins + b];
+      atomicAdd(cell, (unsigned long long)q.x);
+      atomicAdd(cell + hplane, (unsigned long long)q.y);
     }
   }
   __syncthreads();
@@ -864,8 +870,8 @@ __global__ void hist_pair_range_k(
   for (int i2 = tid; i2 < jmax * n_bins; i2 += blockDim.x) {
     const int f = i2 / n_bins;
     const int b = i2 % n_bins;
-    const unsigned long long gsum = lds64[(f * n_bins + b) * 2 + 0];
-    const unsigned long long hpacked = lds64[(f * n_bins + b) * 2 + 1];
+    const unsigned long long gsum = lds64[i2];
+    const unsigned long long hpacked = lds64[hplane + i2];
     if (gsum == 0ull && hpacked == 0ull) continue;
     const unsigned long long cnt = hpacked >> 44;
     const unsigned long long hsum = hpacked & ((1ull << 44) - 1ull);
@@ -879,7 +885,7 @@ __global__ void hist_pair_range_k(
 extern "C" void launch_hist_pair_range(
     const void* pair, const void* ghq, long n_arena, long lo, long m,
     long long* hist, int n_bins, int npairs, int tail_bytes,
-    const int* nl_dev, int side, hipStream_t stream) {
+    const int* nl_dev, int side, long chunk_override, hipStream_t stream) {
   if (m == 0) return;
   long chunks = (2048 + npairs - 1) / npairs;
   long chunk = (m + chunks - 1) / chunks;
@@ -888,6 +894,8 @@ extern "C" void launch_hist_pair_range(
     if (chunk < 2048) chunk = 2048;
     if (chunk > 16384) chunk = 16384;
   }
+  // test/tuning override: whole 256-row tiles, same cap as the policy
+  if (chunk_override > 0) chunk = (chunk_override + 255) / 256 * 256;
   if (chunk > (1l << 19)) chunk = 1l << 19;
   chunks = (m + chunk - 1) / chunk;
   dim3 grid((unsigned)chunks, (unsigned)npairs);
