@@ -800,18 +800,39 @@ extern "C" void launch_partition_arena(
 // range-mode histogram over arena segments: rows are CONTIGUOUS [lo+base,
 // lo+base+m_eff) of a buffer — no index gather at all.  side resolves the
 // child range from the device left count exactly like the rows-list kernel.
-__global__ void hist_pair_range_k(
+//
+// One block = one (row chunk, bin plane) and one 32 KB LDS histogram, shared
+// by however many waves the launcher gives it (256, 512 or 1024 threads).
+// The row loop is bound by the CU's LDS-atomic throughput, not by latency:
+// more waves shorten only the zeroing and the flush (launcher's comment).
+//
+// order 0: grid (chunks, planes).  order 1: 1-D grid in which blocks b and
+// b + 8 (dealt to the same XCD, as observed; nothing depends on it) are the
+// consecutive planes of one chunk, so a chunk's 16-byte gradient records are
+// fetched from HBM by its first plane and from that XCD's L2 by the others.
+// Both widths above 256 and order 1 are there for measurement; the policy
+// uses neither.
+__global__ void __launch_bounds__(1024) hist_pair_range_k(
     const unsigned long long* __restrict__ pair, const longlong2* __restrict__ ghq,
     long n_arena, long lo, long m, long long* __restrict__ hist, int n_bins,
     int npairs, int tail_bytes, long chunk,
-    const int* __restrict__ nl_dev, int side) {
+    const int* __restrict__ nl_dev, int side, int order) {
   long base = 0, m_eff = m;
   if (side >= 0) {
     const long nl = nl_dev[0];
     m_eff = (side == 0) ? nl : m - nl;
     base = (side == 0) ? 0 : nl;
   }
-  if ((long)blockIdx.x * chunk >= m_eff) return;
+  long chunk_id = blockIdx.x;
+  int pair_id = blockIdx.y;
+  if (order == 1) {
+    const long k = blockIdx.x >> 3;
+    pair_id = (int)(k % npairs);
+    chunk_id = (k / npairs) * 8 + (blockIdx.x & 7);
+  }
+  // uniform per block (also drops the padding blocks of order 1): no thread
+  // of a block that leaves here reaches a barrier
+  if (chunk_id * chunk >= m_eff) return;
   extern __shared__ unsigned long long lds64[];
   const int tid = threadIdx.x;
   // two LDS planes at 8-byte stride: all g cells, then all cnt|h cells.
@@ -824,12 +845,11 @@ __global__ void hist_pair_range_k(
   for (int i = tid; i < lds_elems; i += blockDim.x) lds64[i] = 0ull;
   __syncthreads();
 
-  const int pair_id = blockIdx.y;
   const int jmax = (pair_id == npairs - 1) ? tail_bytes : 8;
   const unsigned long long* plane =
       pair + (size_t)pair_id * n_arena + lo + base;
   const longlong2* gh = ghq + lo + base;
-  const long start = (long)blockIdx.x * chunk;
+  const long start = chunk_id * chunk;
   const long end = min(start + chunk, m_eff);
 
   constexpr int ILP = 4;
@@ -867,43 +887,84 @@ __global__ void hist_pair_range_k(
   }
   __syncthreads();
 
-  for (int i2 = tid; i2 < jmax * n_bins; i2 += blockDim.x) {
-    const int f = i2 / n_bins;
-    const int b = i2 % n_bins;
-    const unsigned long long gsum = lds64[i2];
-    const unsigned long long hpacked = lds64[hplane + i2];
-    if (gsum == 0ull && hpacked == 0ull) continue;
-    const unsigned long long cnt = hpacked >> 44;
-    const unsigned long long hsum = hpacked & ((1ull << 44) - 1ull);
-    long long* out = hist + ((size_t)(pair_id * 8 + f) * n_bins + b) * 3;
-    atomicAdd((unsigned long long*)(out + 0), gsum);
-    atomicAdd((unsigned long long*)(out + 1), hsum);
-    atomicAdd((unsigned long long*)(out + 2), cnt);
+  // flush: the plane's jmax * n_bins cells are jmax * n_bins * 3 CONTIGUOUS
+  // int64 slots of the (nf_pad, n_bins, 3) histogram; one slot per lane makes
+  // every wave-instruction 512 contiguous bytes (three atomics per lane at
+  // out+0/+1/+2 spread 64 x 8 B over 1536).  The pad features of the last
+  // plane lie behind slot jmax * n_bins * 3 and are never touched.
+  long long* out = hist + (size_t)pair_id * 8 * n_bins * 3;
+  const int nslots = jmax * n_bins * 3;
+  for (int k = tid; k < nslots; k += blockDim.x) {
+    const int c = k / 3;
+    const int comp = k - 3 * c;
+    unsigned long long v;
+    if (comp == 0) {
+      v = lds64[c];
+    } else {
+      const unsigned long long hpacked = lds64[hplane + c];
+      v = (comp == 1) ? (hpacked & ((1ull << 44) - 1ull)) : (hpacked >> 44);
+    }
+    if (v != 0ull) atomicAdd((unsigned long long*)(out + k), v);
   }
 }
 
+// threads: 256, 512 or 1024, 0 = policy.  order: 0 or 1, -1 = policy.  The
+// caller (gbdt_grower.cpp) has validated both.
 extern "C" void launch_hist_pair_range(
     const void* pair, const void* ghq, long n_arena, long lo, long m,
     long long* hist, int n_bins, int npairs, int tail_bytes,
-    const int* nl_dev, int side, long chunk_override, hipStream_t stream) {
+    const int* nl_dev, int side, long chunk_override, int threads, int order,
+    hipStream_t stream) {
   if (m == 0) return;
-  long chunks = (2048 + npairs - 1) / npairs;
+  // Policy from tools/chain_overlap_probe.py --hist-sweep on MI355X (13
+  // planes, kernel alone, median us of 21 alternated repeats; profiles/
+  // hist_wide_sweep_*.jsonl).  Rows per block, 256 threads, order 0:
+  //   rows     2048   4096   8192  16384  31848  63695
+  //   2^14     12.4   15.1   21.4   33.1
+  //   2^16     24.2   18.2   22.2   34.2   57.5  104.4
+  //   2^17     39.1   28.8   24.6   34.6   59.9  106.1
+  //   2^18     68.9   43.9   37.4   36.6   60.2  108.3
+  //   2^20    236.8  132.4   97.6   98.1  107.6  109.5
+  //   2^22   1016    561    340.8  325.3  347.1  391.2
+  //   5*10^6 1221    670    402.1  395.1  399.8  430.7
+  //   10^7   2475   1345    792.4  762.2  752.8  768.4
+  // The row loop runs at about 1.5 us per 1024 rows of one plane per CU
+  // whatever the width (two thirds of its LDS cycles are bank conflicts of
+  // the 8-byte atomics), so a leaf wants its rows spread over all CUs and no
+  // more flushes than that takes: m / 16 rows per block (208 blocks at 13
+  // planes) between 2048 and 16384; from 2.6M rows up, as many chunks as
+  // keep the grid within 2048 blocks, eight per CU (2048 / npairs rounded
+  // DOWN: one chunk more is a ninth round of six blocks, 806 against 768 us
+  // at 10^7 rows).
+  // Width: 512 and 1024 threads are 1-3 us faster alone up to 2^16 rows
+  // (10.3 -> 7.2 us at 1024 rows, 18.1 -> 17.2 at 2^16) and equal above, but
+  // slower in the whole training step, where a histogram shares the CUs with
+  // other leaves' scatters (9.14 / 9.34 / 9.75 ms per step at 256 / 512 /
+  // 1024): policy 256.  Order 1 halves the bytes fetched at 10^7 rows (L2
+  // hits 1.2M -> 14.2M) and changes neither the kernel's time, which LDS
+  // bounds, nor the step's: policy 0.  docs/benchmarks.md has the numbers.
+  long chunks = 2048 / npairs > 0 ? 2048 / npairs : 1;
   long chunk = (m + chunks - 1) / chunks;
   if (chunk < 16384) {
-    chunk = (m + 7) / 8;
+    chunk = (m + 15) / 16;
     if (chunk < 2048) chunk = 2048;
     if (chunk > 16384) chunk = 16384;
   }
   // test/tuning override: whole 256-row tiles, same cap as the policy
   if (chunk_override > 0) chunk = (chunk_override + 255) / 256 * 256;
+  // the packed LDS cell holds a 20-bit count next to the 44-bit hessian sum,
+  // whatever the block width
   if (chunk > (1l << 19)) chunk = 1l << 19;
   chunks = (m + chunk - 1) / chunk;
+  if (threads == 0) threads = 256;
+  if (order < 0) order = 0;
   dim3 grid((unsigned)chunks, (unsigned)npairs);
+  if (order == 1) grid = dim3((unsigned)((chunks + 7) / 8 * 8 * npairs));
   const size_t lds_bytes = (size_t)8 * n_bins * 2 * sizeof(long long);
-  hipLaunchKernelGGL(hist_pair_range_k, grid, dim3(256), lds_bytes, stream,
-                     (const unsigned long long*)pair, (const longlong2*)ghq,
-                     n_arena, lo, m, hist, n_bins, npairs, tail_bytes, chunk,
-                     nl_dev, side);
+  hipLaunchKernelGGL(hist_pair_range_k, grid, dim3((unsigned)threads),
+                     lds_bytes, stream, (const unsigned long long*)pair,
+                     (const longlong2*)ghq, n_arena, lo, m, hist, n_bins,
+                     npairs, tail_bytes, chunk, nl_dev, side, order);
 }
 
 extern "C" void launch_partition(const void* binned, long n_rows,

@@ -12,6 +12,14 @@ with each kernel's time alone and the spread (p10..p90) of every figure:
 
   python tools/chain_overlap_probe.py [--n-arena 10000000] [--features 100]
 
+With --hist-only M... it times the histogram alone; --threads, --chunk and
+--order force its block width, rows per block and block order (0 / 0 / -1
+leave each to the launcher's policy).  With --hist-sweep M... it alternates,
+within every repeat, the policy and every combination of --sweep-threads,
+--sweep-chunks and --sweep-orders, one JSON line per size and combination:
+
+  python tools/chain_overlap_probe.py --hist-sweep 262144 10000000
+
 With --trace CSV (a rocprofv3 --kernel-trace `*_kernel_trace.csv` of a
 training run) it measures nothing and instead reports for how long intervals
 of the two kernels overlapped in that run:
@@ -92,6 +100,21 @@ def main():
     ap.add_argument("--hist-only", type=int, nargs="*", default=None,
                     metavar="M", help="only time the histogram alone over "
                     "[0, M) for each M (kernel A/B between two builds)")
+    ap.add_argument("--threads", type=int, default=0,
+                    help="histogram block width: 256, 512, 1024; 0 = policy")
+    ap.add_argument("--chunk", type=int, default=0,
+                    help="histogram rows per block; 0 = policy")
+    ap.add_argument("--order", type=int, default=-1,
+                    help="histogram block order: 0 = (chunks, planes) grid, "
+                    "1 = planes of a chunk on one XCD; -1 = policy")
+    ap.add_argument("--hist-sweep", type=int, nargs="*", default=None,
+                    metavar="M", help="sweep width x rows per block x order "
+                    "of the histogram alone over [0, M) for each M")
+    ap.add_argument("--sweep-threads", type=int, nargs="+",
+                    default=[256, 512, 1024])
+    ap.add_argument("--sweep-chunks", type=int, nargs="+",
+                    default=[4096, 16384, 65536])
+    ap.add_argument("--sweep-orders", type=int, nargs="+", default=[0, 1])
     ap.add_argument("--trace", default=None,
                     help="rocprofv3 kernel-trace CSV to analyse instead")
     ap.add_argument("--trees", type=int, default=13,
@@ -124,8 +147,10 @@ def main():
     s_main = torch.cuda.current_stream()
     s_a, s_b = torch.cuda.Stream(), torch.cuda.Stream()
 
-    def run_hist(m):
-        _hip_grower.hist_pair_range(pair, ghq, 0, m, hist, nb, tail)
+    def run_hist(m, threads=args.threads, chunk=args.chunk,
+                 order=args.order):
+        _hip_grower.hist_pair_range(pair, ghq, 0, m, hist, nb, tail,
+                                    chunk=chunk, threads=threads, order=order)
 
     def run_part(m):
         # threshold at the middle bin of feature 17: about half go left
@@ -166,9 +191,32 @@ def main():
             torch.cuda.synchronize()
             ts = [timed(lambda: run_hist(m)) * 1e3
                   for _ in range(args.iters)]
-            print(json.dumps({"m": m, "hist_alone_us": pct(ts, 0.5),
+            print(json.dumps({"m": m, "threads": args.threads,
+                              "chunk": args.chunk, "order": args.order,
+                              "hist_alone_us": pct(ts, 0.5),
                               "p10": pct(ts, 0.1), "p90": pct(ts, 0.9)}),
                   flush=True)
+        return
+
+    if args.hist_sweep is not None:
+        combos = [(0, 0, -1)] + [
+            (t, c, o) for t in args.sweep_threads for c in args.sweep_chunks
+            for o in args.sweep_orders]
+        for m in args.hist_sweep or [1 << 18, n]:
+            m = min(m, n)
+            for cfg in combos:  # warm up every combination
+                run_hist(m, *cfg)
+            torch.cuda.synchronize()
+            ts = {cfg: [] for cfg in combos}
+            for _ in range(args.iters):  # alternate them in every repeat
+                for cfg in combos:
+                    ts[cfg].append(timed(lambda: run_hist(m, *cfg)) * 1e3)
+            for (t, c, o), v in ts.items():
+                print(json.dumps({
+                    "m": m, "threads": t, "chunk": c, "order": o,
+                    "hist_alone_us": round(pct(v, 0.5), 1),
+                    "p10": round(pct(v, 0.1), 1),
+                    "p90": round(pct(v, 0.9), 1)}), flush=True)
         return
 
     for m in args.sizes:
