@@ -59,7 +59,7 @@ void launch_partition_arena(const void*, const void*, const int*, void*,
                             hipStream_t);
 void launch_hist_pair_range(const void*, const void*, long, long, long,
                             long long*, int, int, int, const int*, int, long,
-                            int, int, hipStream_t);
+                            int, int, int, hipStream_t);
 void launch_sibling_scan(const long long*, const long long*, long long*, int,
                          long, int, float, float, float, float, long,
                          const bool*, float*, double, double, hipStream_t);
@@ -108,11 +108,12 @@ int grower_streams_from_env() {
   return (int)v;
 }
 
-// Block width and block order of the range histogram.  An explicit argument
-// wins; else MMLSPARK_AMD_HIST_THREADS (0/256/512/1024) and
-// MMLSPARK_AMD_HIST_ORDER (0/1); else the launcher's policy (threads 0,
-// order -1).  The environment is read at every launch, so one process can
-// switch settings: a getenv is nothing next to a kernel launch.
+// Block width, block order and LDS layout of the range histogram.  An
+// explicit argument wins; else MMLSPARK_AMD_HIST_THREADS (0/256/512/1024),
+// MMLSPARK_AMD_HIST_ORDER (0/1) and MMLSPARK_AMD_HIST_LAYOUT (0/1/2); else
+// the launcher's policy (threads 0, order -1, layout -1).  The environment
+// is read at every launch, so one process can switch settings: a getenv is
+// nothing next to a kernel launch.
 long hist_env(const char* name, long unset) {
   const char* e = std::getenv(name);
   if (!e || !*e) return unset;
@@ -135,6 +136,13 @@ int hist_order(long arg = -1) {
   const long v = arg != -1 ? arg : hist_env("MMLSPARK_AMD_HIST_ORDER", -1);
   TORCH_CHECK(v >= -1 && v <= 1,
               "order / MMLSPARK_AMD_HIST_ORDER must be 0 or 1, got ", v);
+  return (int)v;
+}
+
+int hist_layout(long arg = -1) {
+  const long v = arg != -1 ? arg : hist_env("MMLSPARK_AMD_HIST_LAYOUT", -1);
+  TORCH_CHECK(v >= -1 && v <= 2,
+              "layout / MMLSPARK_AMD_HIST_LAYOUT must be 0, 1 or 2, got ", v);
   return (int)v;
 }
 
@@ -244,7 +252,7 @@ torch::Tensor build_hist(GrowCtx& ctx, int buf, long lo, long m,
       ctx.pair[buf].data_ptr(), ctx.ghq[buf].data_ptr(), ctx.n_arena, lo, m,
       (long long*)hist.data_ptr<int64_t>(), ctx.n_bins, ctx.npairs,
       ctx.tail_bytes, nl_dev, side, 0, hist_threads(), hist_order(),
-      grower_stream());
+      hist_layout(), grower_stream());
   if (ctx.has_reduce) {
     std::vector<at::Tensor> v{hist};
     ctx.pg->allreduce(v)->wait();  // stream-ordered on RCCL; no GIL
@@ -528,6 +536,7 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
   // a bad histogram setting raises here, before any chain is in flight
   (void)hist_threads();
   (void)hist_order();
+  (void)hist_layout();
 
   py::gil_scoped_release nogil;
 
@@ -819,12 +828,13 @@ torch::Tensor partition_arena(torch::Tensor pair_src, torch::Tensor ghq_src,
 // 0 / 1 only the left / right part of the range is read, split at the device
 // count nl_dev[0], which the caller keeps within [0, m], as it keeps every
 // bin byte of the valid features below n_bins: neither can be checked here
-// without reading the arena back.  chunk = 0, threads = 0 and order = -1 take
-// the environment's setting if there is one and else the launcher's policy.
+// without reading the arena back.  chunk = 0, threads = 0, order = -1 and
+// layout = -1 take the environment's setting if there is one and else the
+// launcher's policy.
 void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
                      torch::Tensor hist, long n_bins, long tail_bytes,
                      c10::optional<torch::Tensor> nl_dev, long side,
-                     long chunk, long threads, long order) {
+                     long chunk, long threads, long order, long layout) {
   TORCH_CHECK(pair.is_cuda() && pair.is_contiguous() && pair.dim() == 2 &&
               pair.scalar_type() == torch::kInt64,
               "pair planes: contiguous (npairs, n_arena) i64");
@@ -845,6 +855,7 @@ void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
   TORCH_CHECK(chunk >= 0, "chunk must be >= 0");
   const int threads_r = hist_threads(threads);
   const int order_r = hist_order(order);
+  const int layout_r = hist_layout(layout);
   const int* nl = nullptr;
   if (side >= 0) {
     TORCH_CHECK(nl_dev.has_value() && nl_dev->is_cuda() &&
@@ -855,7 +866,7 @@ void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
   launch_hist_pair_range(pair.data_ptr(), ghq.data_ptr(), n_arena, lo, m,
                          (long long*)hist.data_ptr<int64_t>(), (int)n_bins,
                          (int)npairs, (int)tail_bytes, nl, (int)side, chunk,
-                         threads_r, order_r, grower_stream());
+                         threads_r, order_r, layout_r, grower_stream());
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -874,7 +885,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ghq"), py::arg("lo"), py::arg("m"), py::arg("hist"),
         py::arg("n_bins"), py::arg("tail_bytes"),
         py::arg("nl_dev") = py::none(), py::arg("side") = -1,
-        py::arg("chunk") = 0, py::arg("threads") = 0, py::arg("order") = -1);
+        py::arg("chunk") = 0, py::arg("threads") = 0, py::arg("order") = -1,
+        py::arg("layout") = -1);
   m.def("allreduce_native", &allreduce_native,
         "GIL-free c10d all_reduce through the same C++ path as the grower");
 }

@@ -801,17 +801,79 @@ extern "C" void launch_partition_arena(
 // lo+base+m_eff) of a buffer — no index gather at all.  side resolves the
 // child range from the device left count exactly like the rows-list kernel.
 //
-// One block = one (row chunk, bin plane) and one 32 KB LDS histogram, shared
-// by however many waves the launcher gives it (256, 512 or 1024 threads).
-// The row loop is bound by the CU's LDS-atomic throughput, not by latency:
-// more waves shorten only the zeroing and the flush (launcher's comment).
+// One block = one (row chunk, bin plane) and one LDS histogram of 32 KB, or
+// 64 KB in layout 2, shared by however many waves the launcher gives it (256,
+// 512 or 1024 threads).  With layout 0 the row loop is bound by the CU's
+// LDS-atomic throughput, two thirds of it bank conflicts; layouts 1 and 2
+// take the conflicts out and leave big leaves close to HBM (launcher's
+// comment).
 //
 // order 0: grid (chunks, planes).  order 1: 1-D grid in which blocks b and
 // b + 8 (dealt to the same XCD, as observed; nothing depends on it) are the
 // consecutive planes of one chunk, so a chunk's 16-byte gradient records are
 // fetched from HBM by its first plane and from that XCD's L2 by the others.
-// Both widths above 256 and order 1 are there for measurement; the policy
-// uses neither.
+// The policy uses order 1 and 512 threads with layout 2 only; 1024 threads
+// are there for measurement.
+//
+// LAYOUT picks the LDS cell addressing (compile-time: the row loop carries no
+// layout branch).  An 8-byte LDS atomic is serviced in four groups of 16
+// contiguous lanes over 16 bank pairs (tools/atomic_bench.hip, h_pairX).
+//   0: feature-major, one copy: cell = j * n_bins + b, every lane of a
+//      wave-instruction on the same feature j and a random bin: each group
+//      throws 16 random cells at 16 bank pairs.
+//   1: bin-major, one copy: cell = b * 8 + j, where at step t lane l handles
+//      byte j = (l + t) & 7 of its own word; a group holds every j twice.
+//   2: bin-major, one copy per lane half: cell = b * 16 + (l & 8) + j, bank
+//      pair (l & 8) + j: the 16 lanes of a group hit 16 different bank pairs
+//      whatever the data.  The flush adds the two copies.
+// Layouts 1 and 2 keep the cnt|h plane at the fixed cell offset 256 * stride
+// (a DS instruction offset, not an address add), so their LDS allocation is
+// (256 + n_bins) * stride cells: 32,704 B and 65,408 B at 255 bins.
+// rows of layouts 1 and 2: FULL planes (jmax == 8) need no predicate; in the
+// last plane the lanes whose byte is a pad byte (j >= jmax) sit the step out
+template <int STRIDE, bool FULL>
+DEV_INLINE void hist_rot_row(unsigned long long* lds, int copy, int rot,
+                             int tid, int jmax, unsigned long long v,
+                             longlong2 q) {
+  // byte (tid + t) & 7 of v is byte t of v rotated right by 8 * (tid & 7)
+  const unsigned long long w = (v >> rot) | (v << ((64 - rot) & 63));
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const int j = (tid + t) & 7;
+    if (FULL || j < jmax) {
+      const int b = (int)((w >> (8 * t)) & 0xffull);
+      unsigned long long* cell = lds + b * STRIDE + copy + j;
+      atomicAdd(cell, (unsigned long long)q.x);
+      atomicAdd(cell + 256 * STRIDE, (unsigned long long)q.y);
+    }
+  }
+}
+
+template <int STRIDE, bool FULL>
+DEV_INLINE void hist_rot_rows(unsigned long long* lds, int tid, int jmax,
+                              const unsigned long long* __restrict__ plane,
+                              const longlong2* __restrict__ gh, long start,
+                              long end) {
+  const int copy = STRIDE == 16 ? (tid & 8) : 0;
+  const int rot = 8 * (tid & 7);
+  constexpr int ILP = 4;
+  long i = start + tid;
+  for (; i + (ILP - 1) * (long)blockDim.x < end; i += ILP * blockDim.x) {
+    unsigned long long v[ILP];
+    longlong2 q[ILP];
+#pragma unroll
+    for (int u = 0; u < ILP; ++u) v[u] = plane[i + u * blockDim.x];
+#pragma unroll
+    for (int u = 0; u < ILP; ++u) q[u] = gh[i + u * blockDim.x];
+#pragma unroll
+    for (int u = 0; u < ILP; ++u)
+      hist_rot_row<STRIDE, FULL>(lds, copy, rot, tid, jmax, v[u], q[u]);
+  }
+  for (; i < end; i += blockDim.x)
+    hist_rot_row<STRIDE, FULL>(lds, copy, rot, tid, jmax, plane[i], gh[i]);
+}
+
+template <int LAYOUT>
 __global__ void __launch_bounds__(1024) hist_pair_range_k(
     const unsigned long long* __restrict__ pair, const longlong2* __restrict__ ghq,
     long n_arena, long lo, long m, long long* __restrict__ hist, int n_bins,
@@ -835,120 +897,168 @@ __global__ void __launch_bounds__(1024) hist_pair_range_k(
   if (chunk_id * chunk >= m_eff) return;
   extern __shared__ unsigned long long lds64[];
   const int tid = threadIdx.x;
-  // two LDS planes at 8-byte stride: all g cells, then all cnt|h cells.
-  // Interleaved [g][cnt|h] cells at 16-byte stride put every g atomic of a
-  // wave on one half of the bank pairs and every h atomic on the other;
-  // measured 1068 -> 847 us at 10M rows, 31.0 -> 27.6 us at 2^16
-  // (docs/benchmarks.md)
-  const int hplane = 8 * n_bins;
-  const int lds_elems = 8 * n_bins * 2;
-  for (int i = tid; i < lds_elems; i += blockDim.x) lds64[i] = 0ull;
-  __syncthreads();
-
   const int jmax = (pair_id == npairs - 1) ? tail_bytes : 8;
   const unsigned long long* plane =
       pair + (size_t)pair_id * n_arena + lo + base;
   const longlong2* gh = ghq + lo + base;
   const long start = chunk_id * chunk;
   const long end = min(start + chunk, m_eff);
+  long long* out = hist + (size_t)pair_id * 8 * n_bins * 3;
+  const int nslots = jmax * n_bins * 3;
 
-  constexpr int ILP = 4;
-  long i = start + tid;
-  for (; i + (ILP - 1) * (long)blockDim.x < end; i += ILP * blockDim.x) {
-    unsigned long long v[ILP];
-    longlong2 q[ILP];
+  if constexpr (LAYOUT == 0) {
+    // two LDS planes at 8-byte stride: all g cells, then all cnt|h cells.
+    // Interleaved [g][cnt|h] cells at 16-byte stride put every g atomic of a
+    // wave on one half of the bank pairs and every h atomic on the other;
+    // measured 1068 -> 847 us at 10M rows, 31.0 -> 27.6 us at 2^16
+    // (docs/benchmarks.md)
+    const int hplane = 8 * n_bins;
+    const int lds_elems = 8 * n_bins * 2;
+    for (int i = tid; i < lds_elems; i += blockDim.x) lds64[i] = 0ull;
+    __syncthreads();
+
+    constexpr int ILP = 4;
+    long i = start + tid;
+    for (; i + (ILP - 1) * (long)blockDim.x < end; i += ILP * blockDim.x) {
+      unsigned long long v[ILP];
+      longlong2 q[ILP];
 #pragma unroll
-    for (int u = 0; u < ILP; ++u) v[u] = plane[i + u * blockDim.x];
+      for (int u = 0; u < ILP; ++u) v[u] = plane[i + u * blockDim.x];
 #pragma unroll
-    for (int u = 0; u < ILP; ++u) q[u] = gh[i + u * blockDim.x];
+      for (int u = 0; u < ILP; ++u) q[u] = gh[i + u * blockDim.x];
 #pragma unroll
-    for (int u = 0; u < ILP; ++u) {
+      for (int u = 0; u < ILP; ++u) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (j >= jmax) break;
+          const int b = (int)((v[u] >> (8 * j)) & 0xffull);
+          unsigned long long* cell = &lds64[j * n_bins + b];
+          atomicAdd(cell, (unsigned long long)q[u].x);
+          atomicAdd(cell + hplane, (unsigned long long)q[u].y);
+        }
+      }
+    }
+    for (; i < end; i += blockDim.x) {
+      const unsigned long long v = plane[i];
+      const longlong2 q = gh[i];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (j >= jmax) break;
-        const int b = (int)((v[u] >> (8 * j)) & 0xffull);
+        const int b = (int)((v >> (8 * j)) & 0xffull);
         unsigned long long* cell = &lds64[j * n_bins + b];
-        atomicAdd(cell, (unsigned long long)q[u].x);
-        atomicAdd(cell + hplane, (unsigned long long)q[u].y);
+        atomicAdd(cell, (unsigned long long)q.x);
+        atomicAdd(cell + hplane, (unsigned long long)q.y);
       }
     }
-  }
-  for (; i < end; i += blockDim.x) {
-    const unsigned long long v = plane[i];
-    const longlong2 q = gh[i];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (j >= jmax) break;
-      const int b = (int)((v >> (8 * j)) & 0xffull);
-      unsigned long long* cell = &lds64[j * n_bins + b];
-      atomicAdd(cell, (unsigned long long)q.x);
-      atomicAdd(cell + hplane, (unsigned long long)q.y);
-    }
-  }
-  __syncthreads();
+    __syncthreads();
 
-  // flush: the plane's jmax * n_bins cells are jmax * n_bins * 3 CONTIGUOUS
-  // int64 slots of the (nf_pad, n_bins, 3) histogram; one slot per lane makes
-  // every wave-instruction 512 contiguous bytes (three atomics per lane at
-  // out+0/+1/+2 spread 64 x 8 B over 1536).  The pad features of the last
-  // plane lie behind slot jmax * n_bins * 3 and are never touched.
-  long long* out = hist + (size_t)pair_id * 8 * n_bins * 3;
-  const int nslots = jmax * n_bins * 3;
-  for (int k = tid; k < nslots; k += blockDim.x) {
-    const int c = k / 3;
-    const int comp = k - 3 * c;
-    unsigned long long v;
-    if (comp == 0) {
-      v = lds64[c];
-    } else {
-      const unsigned long long hpacked = lds64[hplane + c];
-      v = (comp == 1) ? (hpacked & ((1ull << 44) - 1ull)) : (hpacked >> 44);
+    // flush: the plane's jmax * n_bins cells are jmax * n_bins * 3 CONTIGUOUS
+    // int64 slots of the (nf_pad, n_bins, 3) histogram; one slot per lane makes
+    // every wave-instruction 512 contiguous bytes (three atomics per lane at
+    // out+0/+1/+2 spread 64 x 8 B over 1536).  The pad features of the last
+    // plane lie behind slot jmax * n_bins * 3 and are never touched.
+    for (int k = tid; k < nslots; k += blockDim.x) {
+      const int c = k / 3;
+      const int comp = k - 3 * c;
+      unsigned long long v;
+      if (comp == 0) {
+        v = lds64[c];
+      } else {
+        const unsigned long long hpacked = lds64[hplane + c];
+        v = (comp == 1) ? (hpacked & ((1ull << 44) - 1ull)) : (hpacked >> 44);
+      }
+      if (v != 0ull) atomicAdd((unsigned long long*)(out + k), v);
     }
-    if (v != 0ull) atomicAdd((unsigned long long*)(out + k), v);
+  } else {
+    constexpr int STRIDE = LAYOUT == 2 ? 16 : 8;
+    constexpr int HP = 256 * STRIDE;  // first cnt|h cell
+    const int used = STRIDE * n_bins;
+    for (int i = tid; i < 2 * used; i += blockDim.x)
+      lds64[i < used ? i : HP + i - used] = 0ull;
+    __syncthreads();
+    if (jmax == 8)
+      hist_rot_rows<STRIDE, true>(lds64, tid, jmax, plane, gh, start, end);
+    else
+      hist_rot_rows<STRIDE, false>(lds64, tid, jmax, plane, gh, start, end);
+    __syncthreads();
+
+    // flush: the same contiguous slots as layout 0, slot k = ((f * n_bins +
+    // b) * 3 + comp), read from cell b * STRIDE + f; layout 2 adds its two
+    // copies before cnt|h is unpacked (both fields are bounded by the
+    // block's rows, not by the copies)
+    for (int k = tid; k < nslots; k += blockDim.x) {
+      const int c = k / 3;
+      const int comp = k - 3 * c;
+      const int f = c / n_bins;
+      const int cell = (c - f * n_bins) * STRIDE + f + (comp == 0 ? 0 : HP);
+      unsigned long long v = lds64[cell];
+      if (LAYOUT == 2) v += lds64[cell + 8];
+      if (comp == 1) v &= (1ull << 44) - 1ull;
+      if (comp == 2) v >>= 44;
+      if (v != 0ull) atomicAdd((unsigned long long*)(out + k), v);
+    }
   }
 }
 
-// threads: 256, 512 or 1024, 0 = policy.  order: 0 or 1, -1 = policy.  The
-// caller (gbdt_grower.cpp) has validated both.
+// threads: 256, 512 or 1024, 0 = policy.  order: 0 or 1, -1 = policy.
+// layout: 0, 1 or 2, -1 = policy.  The caller (gbdt_grower.cpp) has validated
+// all three.
 extern "C" void launch_hist_pair_range(
     const void* pair, const void* ghq, long n_arena, long lo, long m,
     long long* hist, int n_bins, int npairs, int tail_bytes,
     const int* nl_dev, int side, long chunk_override, int threads, int order,
-    hipStream_t stream) {
+    int layout, hipStream_t stream) {
   if (m == 0) return;
   // Policy from tools/chain_overlap_probe.py --hist-sweep on MI355X (13
   // planes, kernel alone, median us of 21 alternated repeats; profiles/
-  // hist_wide_sweep_*.jsonl).  Rows per block, 256 threads, order 0:
-  //   rows     2048   4096   8192  16384  31848  63695
-  //   2^14     12.4   15.1   21.4   33.1
-  //   2^16     24.2   18.2   22.2   34.2   57.5  104.4
-  //   2^17     39.1   28.8   24.6   34.6   59.9  106.1
-  //   2^18     68.9   43.9   37.4   36.6   60.2  108.3
-  //   2^20    236.8  132.4   97.6   98.1  107.6  109.5
-  //   2^22   1016    561    340.8  325.3  347.1  391.2
-  //   5*10^6 1221    670    402.1  395.1  399.8  430.7
-  //   10^7   2475   1345    792.4  762.2  752.8  768.4
-  // The row loop runs at about 1.5 us per 1024 rows of one plane per CU
-  // whatever the width (two thirds of its LDS cycles are bank conflicts of
-  // the 8-byte atomics), so a leaf wants its rows spread over all CUs and no
-  // more flushes than that takes: m / 16 rows per block (208 blocks at 13
-  // planes) between 2048 and 16384; from 2.6M rows up, as many chunks as
-  // keep the grid within 2048 blocks, eight per CU (2048 / npairs rounded
-  // DOWN: one chunk more is a ninth round of six blocks, 806 against 768 us
-  // at 10^7 rows).
-  // Width: 512 and 1024 threads are 1-3 us faster alone up to 2^16 rows
-  // (10.3 -> 7.2 us at 1024 rows, 18.1 -> 17.2 at 2^16) and equal above, but
-  // slower in the whole training step, where a histogram shares the CUs with
-  // other leaves' scatters (9.14 / 9.34 / 9.75 ms per step at 256 / 512 /
-  // 1024): policy 256.  Order 1 halves the bytes fetched at 10^7 rows (L2
-  // hits 1.2M -> 14.2M) and changes neither the kernel's time, which LDS
-  // bounds, nor the step's: policy 0.  docs/benchmarks.md has the numbers.
+  // hist_bank_sweep.jsonl).  Rows per block, order 0:
+  //   layout 1, 256 threads
+  //   rows     2048   4096   8192  16384  32768  65536
+  //   2^14     11.3   13.1   17.0   25.6
+  //   2^16     23.6   16.7   18.6   27.9   47.6   89.7
+  //   2^18     65.4   39.3   31.3   31.6   49.8   90.7
+  //   2^20    238.1  129.1   84.3   80.6   78.2   93.3
+  //   2^22   1011    535    307.2  229.7  234.1  266.9
+  //   10^7   2463   1292    735.2  513.2  506.5  507.5
+  //   layout 2, 512 threads (order 1 in brackets)
+  //   2^14     11.1   12.4   15.2   20.8
+  //   2^16     23.1   15.8   16.3   22.2   34.2   59.5
+  //   2^18     66.8   41.1   29.6   25.6   35.0   59.6
+  //   2^20    255.4  138.7   87.8   75.5   63.3   64.0   (62.7 at 32768)
+  //   2^22   1073    571    338.2  251.4  207.6  217.0   (205.6 at 32768)
+  //   10^7   2587   1391    794.6  536.9  484.4  462.4   (428.1 at 65536)
+  // Layout 0 (feature-major cells, 256 threads, the rule below) took 12.2 /
+  // 18.3 / 36.9 / 97.8 / 332.7 / 755.6 us in the same runs: two thirds of
+  // its LDS cycles were bank conflicts.  Without them a block works through
+  // 1024 rows of a plane in about 1.0 us (1.5 before), and from 2^22 rows up
+  // the kernel moves 3.1 GB in under 0.5 ms: HBM is the next bound, which is
+  // why order 1 (a chunk's gradient records fetched once per XCD) now pays
+  // at 10^7 rows.
+  // Layout: 2 from 2^18 rows, where its 64 KB blocks of 512 threads beat
+  // layout 1 by 18 % and more; 1 below, where zeroing and flushing two copies
+  // for 2048-row blocks costs what the conflicts saved (2^14: 11.3 us against
+  // 13.0 for layout 2 at 256 threads).
+  // Rows per block: a leaf wants its rows spread over all CUs and no more
+  // flushes than that takes: m / 16 rows per block (208 blocks at 13 planes)
+  // between 2048 and 16384, 32768 for layout 2, which has two blocks per CU
+  // and not eight; from there up, as many chunks as keep the grid within
+  // 2048 blocks (2048 / npairs rounded down).
+  // Width: 256 threads for layouts 0 and 1 (512 and 1024 are 1-4 us faster
+  // alone and were slower in the whole step for layout 0, 9.14 / 9.34 / 9.75
+  // ms), 512 for layout 2, whose two blocks per CU would otherwise be eight
+  // waves.  Order 1 for layout 2 from 2^20 rows.  In the whole step every
+  // layout-1 and layout-2 shape measured 0.5-0.6 ms under layout 0 and
+  // within 0.1 ms of the others; docs/benchmarks.md has the numbers.
+  if (layout < 0) layout = m >= (1l << 18) ? 2 : 1;
+  // layout 2 has two 64 KB blocks per CU: wider blocks of more rows each
+  const bool wide = layout == 2;
+  const long chunk_cap = wide ? 32768 : 16384;
   long chunks = 2048 / npairs > 0 ? 2048 / npairs : 1;
   long chunk = (m + chunks - 1) / chunks;
-  if (chunk < 16384) {
+  if (chunk < chunk_cap) {
     chunk = (m + 15) / 16;
     if (chunk < 2048) chunk = 2048;
-    if (chunk > 16384) chunk = 16384;
+    if (chunk > chunk_cap) chunk = chunk_cap;
   }
   // test/tuning override: whole 256-row tiles, same cap as the policy
   if (chunk_override > 0) chunk = (chunk_override + 255) / 256 * 256;
@@ -956,15 +1066,23 @@ extern "C" void launch_hist_pair_range(
   // whatever the block width
   if (chunk > (1l << 19)) chunk = 1l << 19;
   chunks = (m + chunk - 1) / chunk;
-  if (threads == 0) threads = 256;
-  if (order < 0) order = 0;
+  if (threads == 0) threads = wide ? 512 : 256;
+  if (order < 0) order = wide && m >= (1l << 20) ? 1 : 0;
   dim3 grid((unsigned)chunks, (unsigned)npairs);
   if (order == 1) grid = dim3((unsigned)((chunks + 7) / 8 * 8 * npairs));
-  const size_t lds_bytes = (size_t)8 * n_bins * 2 * sizeof(long long);
-  hipLaunchKernelGGL(hist_pair_range_k, grid, dim3((unsigned)threads),
-                     lds_bytes, stream, (const unsigned long long*)pair,
-                     (const longlong2*)ghq, n_arena, lo, m, hist, n_bins,
-                     npairs, tail_bytes, chunk, nl_dev, side, order);
+  // layouts 1 and 2: cnt|h plane at cell 256 * stride (kernel's comment); at
+  // most 65,536 B, the most a launch gets without a function attribute
+  const int stride = layout == 2 ? 16 : 8;
+  const size_t lds_bytes =
+      (layout == 0 ? (size_t)8 * n_bins * 2 : (size_t)(256 + n_bins) * stride) *
+      sizeof(long long);
+  auto kern = layout == 0   ? hist_pair_range_k<0>
+              : layout == 1 ? hist_pair_range_k<1>
+                            : hist_pair_range_k<2>;
+  hipLaunchKernelGGL(kern, grid, dim3((unsigned)threads), lds_bytes, stream,
+                     (const unsigned long long*)pair, (const longlong2*)ghq,
+                     n_arena, lo, m, hist, n_bins, npairs, tail_bytes, chunk,
+                     nl_dev, side, order);
 }
 
 extern "C" void launch_partition(const void* binned, long n_rows,

@@ -12,11 +12,13 @@ with each kernel's time alone and the spread (p10..p90) of every figure:
 
   python tools/chain_overlap_probe.py [--n-arena 10000000] [--features 100]
 
-With --hist-only M... it times the histogram alone; --threads, --chunk and
---order force its block width, rows per block and block order (0 / 0 / -1
-leave each to the launcher's policy).  With --hist-sweep M... it alternates,
-within every repeat, the policy and every combination of --sweep-threads,
---sweep-chunks and --sweep-orders, one JSON line per size and combination:
+With --hist-only M... it times the histogram alone; --threads, --chunk,
+--order and --layout force its block width, rows per block, block order and
+LDS cell layout (0 / 0 / -1 / -1 leave each to the launcher's policy); with
+several --layout values they are alternated within every repeat.  With
+--hist-sweep M... it alternates, within every repeat, the policy and every
+combination of --sweep-threads, --sweep-chunks, --sweep-orders and --layout,
+one JSON line per size and combination:
 
   python tools/chain_overlap_probe.py --hist-sweep 262144 10000000
 
@@ -70,7 +72,8 @@ def trace_report(path, trees):
         for row in csv.DictReader(f):
             name = row["Kernel_Name"]
             for k in iv:
-                if name.startswith(k):
+                # template instances are named "void hist_pair_range_k<2>(…"
+                if name.startswith(k) or name.startswith("void " + k):
                     iv[k].append((int(row["Start_Timestamp"]),
                                   int(row["End_Timestamp"])))
     busy = {k: sum(e - s for s, e in v) for k, v in iv.items()}
@@ -107,6 +110,9 @@ def main():
     ap.add_argument("--order", type=int, default=-1,
                     help="histogram block order: 0 = (chunks, planes) grid, "
                     "1 = planes of a chunk on one XCD; -1 = policy")
+    ap.add_argument("--layout", type=int, nargs="+", default=[-1],
+                    help="histogram LDS layout(s): 0 = feature-major, 1 = "
+                    "rotated bin-major, 2 = rotated, two copies; -1 = policy")
     ap.add_argument("--hist-sweep", type=int, nargs="*", default=None,
                     metavar="M", help="sweep width x rows per block x order "
                     "of the histogram alone over [0, M) for each M")
@@ -148,9 +154,10 @@ def main():
     s_a, s_b = torch.cuda.Stream(), torch.cuda.Stream()
 
     def run_hist(m, threads=args.threads, chunk=args.chunk,
-                 order=args.order):
+                 order=args.order, layout=args.layout[0]):
         _hip_grower.hist_pair_range(pair, ghq, 0, m, hist, nb, tail,
-                                    chunk=chunk, threads=threads, order=order)
+                                    chunk=chunk, threads=threads, order=order,
+                                    layout=layout)
 
     def run_part(m):
         # threshold at the middle bin of feature 17: about half go left
@@ -187,20 +194,27 @@ def main():
     if args.hist_only is not None:
         for m in args.hist_only or [1 << 16, n]:
             m = min(m, n)
-            run_hist(m)
+            for lay in args.layout:
+                run_hist(m, layout=lay)
             torch.cuda.synchronize()
-            ts = [timed(lambda: run_hist(m)) * 1e3
-                  for _ in range(args.iters)]
-            print(json.dumps({"m": m, "threads": args.threads,
-                              "chunk": args.chunk, "order": args.order,
-                              "hist_alone_us": pct(ts, 0.5),
-                              "p10": pct(ts, 0.1), "p90": pct(ts, 0.9)}),
-                  flush=True)
+            ts = {lay: [] for lay in args.layout}
+            for _ in range(args.iters):  # alternate the layouts
+                for lay in args.layout:
+                    ts[lay].append(
+                        timed(lambda: run_hist(m, layout=lay)) * 1e3)
+            for lay, v in ts.items():
+                print(json.dumps({"m": m, "threads": args.threads,
+                                  "chunk": args.chunk, "order": args.order,
+                                  "layout": lay,
+                                  "hist_alone_us": pct(v, 0.5),
+                                  "p10": pct(v, 0.1), "p90": pct(v, 0.9)}),
+                      flush=True)
         return
 
     if args.hist_sweep is not None:
-        combos = [(0, 0, -1)] + [
-            (t, c, o) for t in args.sweep_threads for c in args.sweep_chunks
+        combos = [(0, 0, -1, -1)] + [
+            (t, c, o, lay) for lay in args.layout
+            for t in args.sweep_threads for c in args.sweep_chunks
             for o in args.sweep_orders]
         for m in args.hist_sweep or [1 << 18, n]:
             m = min(m, n)
@@ -211,9 +225,10 @@ def main():
             for _ in range(args.iters):  # alternate them in every repeat
                 for cfg in combos:
                     ts[cfg].append(timed(lambda: run_hist(m, *cfg)) * 1e3)
-            for (t, c, o), v in ts.items():
+            for (t, c, o, lay), v in ts.items():
                 print(json.dumps({
                     "m": m, "threads": t, "chunk": c, "order": o,
+                    "layout": lay,
                     "hist_alone_us": round(pct(v, 0.5), 1),
                     "p10": round(pct(v, 0.1), 1),
                     "p90": round(pct(v, 0.9), 1)}), flush=True)
