@@ -916,7 +916,7 @@ ml_language_detector_v2 <- function(url = NULL, subscriptionKey = NULL, subscrip
   stage
 }
 
-ml_light_gbm_classification_model <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, predictionCol = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, boosterModelStr = NULL, startIteration = NULL, numIterations = NULL, device = NULL, rawPredictionCol = NULL, probabilityCol = NULL, thresholds = NULL, isUnbalance = NULL) {
+ml_light_gbm_classification_model <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, predictionCol = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, featuresShapSparse = NULL, boosterModelStr = NULL, startIteration = NULL, numIterations = NULL, device = NULL, rawPredictionCol = NULL, probabilityCol = NULL, thresholds = NULL, isUnbalance = NULL) {
   stage <- mmlspark_amd$models$gbdt$estimators$LightGBMClassificationModel()
   if (!is.null(labelCol)) stage$set("labelCol", labelCol)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
@@ -924,6 +924,7 @@ ml_light_gbm_classification_model <- function(labelCol = NULL, featuresCol = NUL
   if (!is.null(predictionCol)) stage$set("predictionCol", predictionCol)
   if (!is.null(leafPredictionCol)) stage$set("leafPredictionCol", leafPredictionCol)
   if (!is.null(featuresShapCol)) stage$set("featuresShapCol", featuresShapCol)
+  if (!is.null(featuresShapSparse)) stage$set("featuresShapSparse", featuresShapSparse)
   if (!is.null(boosterModelStr)) stage$set("boosterModelStr", boosterModelStr)
   if (!is.null(startIteration)) stage$set("startIteration", startIteration)
   if (!is.null(numIterations)) stage$set("numIterations", numIterations)
@@ -935,7 +936,7 @@ ml_light_gbm_classification_model <- function(labelCol = NULL, featuresCol = NUL
   stage
 }
 
-ml_light_gbm_classifier <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, weightCol = NULL, validationIndicatorCol = NULL, initScoreCol = NULL, predictionCol = NULL, numIterations = NULL, learningRate = NULL, numLeaves = NULL, maxDepth = NULL, maxBin = NULL, lambdaL1 = NULL, lambdaL2 = NULL, minDataInLeaf = NULL, minSumHessianInLeaf = NULL, minGainToSplit = NULL, featureFraction = NULL, baggingFraction = NULL, baggingFreq = NULL, baggingSeed = NULL, boostingType = NULL, topRate = NULL, otherRate = NULL, dropRate = NULL, skipDrop = NULL, maxDrop = NULL, maxDeltaStep = NULL, earlyStoppingRound = NULL, objective = NULL, metric = NULL, seed = NULL, numBatches = NULL, verbosity = NULL, isProvideTrainingMetric = NULL, useBarrierExecutionMode = NULL, parallelism = NULL, topK = NULL, categoricalSlotIndexes = NULL, categoricalSlotNames = NULL, slotNames = NULL, modelString = NULL, lightGBMBooster = NULL, fobj = NULL, boostFromAverage = NULL, improvementTolerance = NULL, posBaggingFraction = NULL, negBaggingFraction = NULL, binSampleCount = NULL, maxBinByFeature = NULL, uniformDrop = NULL, xgboostDartMode = NULL, startIteration = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, chunkSize = NULL, defaultListenPort = NULL, driverListenPort = NULL, timeout = NULL, numTasks = NULL, numThreads = NULL, useSingleDatasetMode = NULL, matrixType = NULL, checkpointDir = NULL, checkpointInterval = NULL, device = NULL, rawPredictionCol = NULL, probabilityCol = NULL, isUnbalance = NULL) {
+ml_light_gbm_classifier <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, weightCol = NULL, validationIndicatorCol = NULL, initScoreCol = NULL, predictionCol = NULL, numIterations = NULL, learningRate = NULL, numLeaves = NULL, maxDepth = NULL, maxBin = NULL, lambdaL1 = NULL, lambdaL2 = NULL, minDataInLeaf = NULL, minSumHessianInLeaf = NULL, minGainToSplit = NULL, featureFraction = NULL, baggingFraction = NULL, baggingFreq = NULL, baggingSeed = NULL, boostingType = NULL, topRate = NULL, otherRate = NULL, dropRate = NULL, skipDrop = NULL, maxDrop = NULL, maxDeltaStep = NULL, earlyStoppingRound = NULL, objective = NULL, metric = NULL, seed = NULL, numBatches = NULL, verbosity = NULL, isProvideTrainingMetric = NULL, useBarrierExecutionMode = NULL, parallelism = NULL, topK = NULL, categoricalSlotIndexes = NULL, categoricalSlotNames = NULL, slotNames = NULL, modelString = NULL, lightGBMBooster = NULL, fobj = NULL, boostFromAverage = NULL, improvementTolerance = NULL, posBaggingFraction = NULL, negBaggingFraction = NULL, binSampleCount = NULL, maxBinByFeature = NULL, uniformDrop = NULL, xgboostDartMode = NULL, startIteration = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, featuresShapSparse = NULL, chunkSize = NULL, defaultListenPort = NULL, driverListenPort = NULL, timeout = NULL, numTasks = NULL, numThreads = NULL, useSingleDatasetMode = NULL, matrixType = NULL, checkpointDir = NULL, checkpointInterval = NULL, device = NULL, rawPredictionCol = NULL, probabilityCol = NULL, isUnbalance = NULL) {
   stage <- mmlspark_amd$models$gbdt$estimators$LightGBMClassifier()
   if (!is.null(labelCol)) stage$set("labelCol", labelCol)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
@@ -992,6 +993,7 @@ ml_light_gbm_classifier <- function(labelCol = NULL, featuresCol = NULL, feature
   if (!is.null(startIteration)) stage$set("startIteration", startIteration)
   if (!is.null(leafPredictionCol)) stage$set("leafPredictionCol", leafPredictionCol)
   if (!is.null(featuresShapCol)) stage$set("featuresShapCol", featuresShapCol)
+  if (!is.null(featuresShapSparse)) stage$set("featuresShapSparse", featuresShapSparse)
   if (!is.null(chunkSize)) stage$set("chunkSize", chunkSize)
   if (!is.null(defaultListenPort)) stage$set("defaultListenPort", defaultListenPort)
   if (!is.null(driverListenPort)) stage$set("driverListenPort", driverListenPort)
@@ -1009,7 +1011,7 @@ ml_light_gbm_classifier <- function(labelCol = NULL, featuresCol = NULL, feature
   stage
 }
 
-ml_light_gbm_ranker <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, weightCol = NULL, validationIndicatorCol = NULL, initScoreCol = NULL, predictionCol = NULL, numIterations = NULL, learningRate = NULL, numLeaves = NULL, maxDepth = NULL, maxBin = NULL, lambdaL1 = NULL, lambdaL2 = NULL, minDataInLeaf = NULL, minSumHessianInLeaf = NULL, minGainToSplit = NULL, featureFraction = NULL, baggingFraction = NULL, baggingFreq = NULL, baggingSeed = NULL, boostingType = NULL, topRate = NULL, otherRate = NULL, dropRate = NULL, skipDrop = NULL, maxDrop = NULL, maxDeltaStep = NULL, earlyStoppingRound = NULL, objective = NULL, metric = NULL, seed = NULL, numBatches = NULL, verbosity = NULL, isProvideTrainingMetric = NULL, useBarrierExecutionMode = NULL, parallelism = NULL, topK = NULL, categoricalSlotIndexes = NULL, categoricalSlotNames = NULL, slotNames = NULL, modelString = NULL, lightGBMBooster = NULL, fobj = NULL, boostFromAverage = NULL, improvementTolerance = NULL, posBaggingFraction = NULL, negBaggingFraction = NULL, binSampleCount = NULL, maxBinByFeature = NULL, uniformDrop = NULL, xgboostDartMode = NULL, startIteration = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, chunkSize = NULL, defaultListenPort = NULL, driverListenPort = NULL, timeout = NULL, numTasks = NULL, numThreads = NULL, useSingleDatasetMode = NULL, matrixType = NULL, checkpointDir = NULL, checkpointInterval = NULL, device = NULL, groupCol = NULL, labelGain = NULL, maxPosition = NULL, evalAt = NULL, repartitionByGroupingColumn = NULL) {
+ml_light_gbm_ranker <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, weightCol = NULL, validationIndicatorCol = NULL, initScoreCol = NULL, predictionCol = NULL, numIterations = NULL, learningRate = NULL, numLeaves = NULL, maxDepth = NULL, maxBin = NULL, lambdaL1 = NULL, lambdaL2 = NULL, minDataInLeaf = NULL, minSumHessianInLeaf = NULL, minGainToSplit = NULL, featureFraction = NULL, baggingFraction = NULL, baggingFreq = NULL, baggingSeed = NULL, boostingType = NULL, topRate = NULL, otherRate = NULL, dropRate = NULL, skipDrop = NULL, maxDrop = NULL, maxDeltaStep = NULL, earlyStoppingRound = NULL, objective = NULL, metric = NULL, seed = NULL, numBatches = NULL, verbosity = NULL, isProvideTrainingMetric = NULL, useBarrierExecutionMode = NULL, parallelism = NULL, topK = NULL, categoricalSlotIndexes = NULL, categoricalSlotNames = NULL, slotNames = NULL, modelString = NULL, lightGBMBooster = NULL, fobj = NULL, boostFromAverage = NULL, improvementTolerance = NULL, posBaggingFraction = NULL, negBaggingFraction = NULL, binSampleCount = NULL, maxBinByFeature = NULL, uniformDrop = NULL, xgboostDartMode = NULL, startIteration = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, featuresShapSparse = NULL, chunkSize = NULL, defaultListenPort = NULL, driverListenPort = NULL, timeout = NULL, numTasks = NULL, numThreads = NULL, useSingleDatasetMode = NULL, matrixType = NULL, checkpointDir = NULL, checkpointInterval = NULL, device = NULL, groupCol = NULL, labelGain = NULL, maxPosition = NULL, evalAt = NULL, repartitionByGroupingColumn = NULL) {
   stage <- mmlspark_amd$models$gbdt$estimators$LightGBMRanker()
   if (!is.null(labelCol)) stage$set("labelCol", labelCol)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
@@ -1066,6 +1068,7 @@ ml_light_gbm_ranker <- function(labelCol = NULL, featuresCol = NULL, featureCols
   if (!is.null(startIteration)) stage$set("startIteration", startIteration)
   if (!is.null(leafPredictionCol)) stage$set("leafPredictionCol", leafPredictionCol)
   if (!is.null(featuresShapCol)) stage$set("featuresShapCol", featuresShapCol)
+  if (!is.null(featuresShapSparse)) stage$set("featuresShapSparse", featuresShapSparse)
   if (!is.null(chunkSize)) stage$set("chunkSize", chunkSize)
   if (!is.null(defaultListenPort)) stage$set("defaultListenPort", defaultListenPort)
   if (!is.null(driverListenPort)) stage$set("driverListenPort", driverListenPort)
@@ -1085,7 +1088,7 @@ ml_light_gbm_ranker <- function(labelCol = NULL, featuresCol = NULL, featureCols
   stage
 }
 
-ml_light_gbm_ranker_model <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, predictionCol = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, boosterModelStr = NULL, startIteration = NULL, numIterations = NULL, device = NULL, labelGain = NULL, maxPosition = NULL, evalAt = NULL) {
+ml_light_gbm_ranker_model <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, predictionCol = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, featuresShapSparse = NULL, boosterModelStr = NULL, startIteration = NULL, numIterations = NULL, device = NULL, labelGain = NULL, maxPosition = NULL, evalAt = NULL) {
   stage <- mmlspark_amd$models$gbdt$estimators$LightGBMRankerModel()
   if (!is.null(labelCol)) stage$set("labelCol", labelCol)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
@@ -1093,6 +1096,7 @@ ml_light_gbm_ranker_model <- function(labelCol = NULL, featuresCol = NULL, featu
   if (!is.null(predictionCol)) stage$set("predictionCol", predictionCol)
   if (!is.null(leafPredictionCol)) stage$set("leafPredictionCol", leafPredictionCol)
   if (!is.null(featuresShapCol)) stage$set("featuresShapCol", featuresShapCol)
+  if (!is.null(featuresShapSparse)) stage$set("featuresShapSparse", featuresShapSparse)
   if (!is.null(boosterModelStr)) stage$set("boosterModelStr", boosterModelStr)
   if (!is.null(startIteration)) stage$set("startIteration", startIteration)
   if (!is.null(numIterations)) stage$set("numIterations", numIterations)
@@ -1103,7 +1107,7 @@ ml_light_gbm_ranker_model <- function(labelCol = NULL, featuresCol = NULL, featu
   stage
 }
 
-ml_light_gbm_regression_model <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, predictionCol = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, boosterModelStr = NULL, startIteration = NULL, numIterations = NULL, device = NULL, alpha = NULL, tweedieVariancePower = NULL) {
+ml_light_gbm_regression_model <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, predictionCol = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, featuresShapSparse = NULL, boosterModelStr = NULL, startIteration = NULL, numIterations = NULL, device = NULL, alpha = NULL, tweedieVariancePower = NULL) {
   stage <- mmlspark_amd$models$gbdt$estimators$LightGBMRegressionModel()
   if (!is.null(labelCol)) stage$set("labelCol", labelCol)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
@@ -1111,6 +1115,7 @@ ml_light_gbm_regression_model <- function(labelCol = NULL, featuresCol = NULL, f
   if (!is.null(predictionCol)) stage$set("predictionCol", predictionCol)
   if (!is.null(leafPredictionCol)) stage$set("leafPredictionCol", leafPredictionCol)
   if (!is.null(featuresShapCol)) stage$set("featuresShapCol", featuresShapCol)
+  if (!is.null(featuresShapSparse)) stage$set("featuresShapSparse", featuresShapSparse)
   if (!is.null(boosterModelStr)) stage$set("boosterModelStr", boosterModelStr)
   if (!is.null(startIteration)) stage$set("startIteration", startIteration)
   if (!is.null(numIterations)) stage$set("numIterations", numIterations)
@@ -1120,7 +1125,7 @@ ml_light_gbm_regression_model <- function(labelCol = NULL, featuresCol = NULL, f
   stage
 }
 
-ml_light_gbm_regressor <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, weightCol = NULL, validationIndicatorCol = NULL, initScoreCol = NULL, predictionCol = NULL, numIterations = NULL, learningRate = NULL, numLeaves = NULL, maxDepth = NULL, maxBin = NULL, lambdaL1 = NULL, lambdaL2 = NULL, minDataInLeaf = NULL, minSumHessianInLeaf = NULL, minGainToSplit = NULL, featureFraction = NULL, baggingFraction = NULL, baggingFreq = NULL, baggingSeed = NULL, boostingType = NULL, topRate = NULL, otherRate = NULL, dropRate = NULL, skipDrop = NULL, maxDrop = NULL, maxDeltaStep = NULL, earlyStoppingRound = NULL, objective = NULL, metric = NULL, seed = NULL, numBatches = NULL, verbosity = NULL, isProvideTrainingMetric = NULL, useBarrierExecutionMode = NULL, parallelism = NULL, topK = NULL, categoricalSlotIndexes = NULL, categoricalSlotNames = NULL, slotNames = NULL, modelString = NULL, lightGBMBooster = NULL, fobj = NULL, boostFromAverage = NULL, improvementTolerance = NULL, posBaggingFraction = NULL, negBaggingFraction = NULL, binSampleCount = NULL, maxBinByFeature = NULL, uniformDrop = NULL, xgboostDartMode = NULL, startIteration = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, chunkSize = NULL, defaultListenPort = NULL, driverListenPort = NULL, timeout = NULL, numTasks = NULL, numThreads = NULL, useSingleDatasetMode = NULL, matrixType = NULL, checkpointDir = NULL, checkpointInterval = NULL, device = NULL, alpha = NULL, tweedieVariancePower = NULL) {
+ml_light_gbm_regressor <- function(labelCol = NULL, featuresCol = NULL, featureCols = NULL, weightCol = NULL, validationIndicatorCol = NULL, initScoreCol = NULL, predictionCol = NULL, numIterations = NULL, learningRate = NULL, numLeaves = NULL, maxDepth = NULL, maxBin = NULL, lambdaL1 = NULL, lambdaL2 = NULL, minDataInLeaf = NULL, minSumHessianInLeaf = NULL, minGainToSplit = NULL, featureFraction = NULL, baggingFraction = NULL, baggingFreq = NULL, baggingSeed = NULL, boostingType = NULL, topRate = NULL, otherRate = NULL, dropRate = NULL, skipDrop = NULL, maxDrop = NULL, maxDeltaStep = NULL, earlyStoppingRound = NULL, objective = NULL, metric = NULL, seed = NULL, numBatches = NULL, verbosity = NULL, isProvideTrainingMetric = NULL, useBarrierExecutionMode = NULL, parallelism = NULL, topK = NULL, categoricalSlotIndexes = NULL, categoricalSlotNames = NULL, slotNames = NULL, modelString = NULL, lightGBMBooster = NULL, fobj = NULL, boostFromAverage = NULL, improvementTolerance = NULL, posBaggingFraction = NULL, negBaggingFraction = NULL, binSampleCount = NULL, maxBinByFeature = NULL, uniformDrop = NULL, xgboostDartMode = NULL, startIteration = NULL, leafPredictionCol = NULL, featuresShapCol = NULL, featuresShapSparse = NULL, chunkSize = NULL, defaultListenPort = NULL, driverListenPort = NULL, timeout = NULL, numTasks = NULL, numThreads = NULL, useSingleDatasetMode = NULL, matrixType = NULL, checkpointDir = NULL, checkpointInterval = NULL, device = NULL, alpha = NULL, tweedieVariancePower = NULL) {
   stage <- mmlspark_amd$models$gbdt$estimators$LightGBMRegressor()
   if (!is.null(labelCol)) stage$set("labelCol", labelCol)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
@@ -1177,6 +1182,7 @@ ml_light_gbm_regressor <- function(labelCol = NULL, featuresCol = NULL, featureC
   if (!is.null(startIteration)) stage$set("startIteration", startIteration)
   if (!is.null(leafPredictionCol)) stage$set("leafPredictionCol", leafPredictionCol)
   if (!is.null(featuresShapCol)) stage$set("featuresShapCol", featuresShapCol)
+  if (!is.null(featuresShapSparse)) stage$set("featuresShapSparse", featuresShapSparse)
   if (!is.null(chunkSize)) stage$set("chunkSize", chunkSize)
   if (!is.null(defaultListenPort)) stage$set("defaultListenPort", defaultListenPort)
   if (!is.null(driverListenPort)) stage$set("driverListenPort", driverListenPort)

@@ -156,19 +156,132 @@ class Booster:
             totals[ti % self.n_outputs] += rec(0) if t.n_nodes else 0.0
         return totals
 
+    def used_features(self) -> np.ndarray:
+        """Sorted int64 array of the distinct features the forest splits
+        on — the only features TreeSHAP can credit."""
+        if "used_features" not in self._flat_cache:
+            parts = [t.feature[t.feature >= 0] for t in self.trees]
+            self._flat_cache["used_features"] = (
+                np.unique(np.concatenate(parts)).astype(np.int64) if parts
+                else np.zeros(0, dtype=np.int64))
+        return self._flat_cache["used_features"]
+
+    def _shap_flat(self, device):
+        """Per-node arrays the CSR TreeSHAP op takes besides _flat's: leaf
+        values folded with the tree weights, float32 covers, and each
+        interior node's slot in used_features()."""
+        key = "shap:" + str(device)
+        if key not in self._flat_cache:
+            fw = flatten_trees(self.trees)
+            scaled = fw["value"].copy()
+            for t in range(len(self.trees)):
+                s, e = fw["offsets"][t], fw["offsets"][t + 1]
+                scaled[s:e] *= float(self.tree_weights[t])
+            cnt = (np.concatenate([t.count for t in self.trees])
+                   .astype(np.float32) if self.trees
+                   else np.zeros(0, dtype=np.float32))
+            feat = fw["feature"]
+            slot = np.where(
+                feat >= 0,
+                np.searchsorted(self.used_features(), np.maximum(feat, 0)),
+                -1).astype(np.int32)
+            self._flat_cache[key] = {
+                "value": torch.from_numpy(scaled).to(device),
+                "count": torch.from_numpy(cnt).to(device),
+                "slot": torch.from_numpy(slot).to(device)}
+        return self._flat_cache[key]
+
+    def predict_contrib_sparse(self, X, max_blocks: int = 0):
+        """TreeSHAP contributions of a CsrMatrix in compact form:
+        (features, values).  features is used_features() (U of them);
+        values is float32 (n, K, U + 1) on X's device — values[:, k, j] is
+        the contribution of features[j] to class k, values[:, k, U] the
+        expected value.  Every other feature's contribution is exactly 0, so
+        nothing of the matrix width is allocated.  On the GPU the rows are
+        read as CSR by tree_shap_csr_k (max_blocks > 0 overrides its grid
+        policy); trees of depth >= 32 go to the CPU path, as in
+        predict_contrib.  The CPU path is predict_contrib's own per-row
+        recursion (Tree.shap_values) over the U used columns only, so that
+        on the CPU a CsrMatrix and its densified copy get the same bits."""
+        feats = self.used_features()
+        U, K, n = int(feats.size), self.n_outputs, X.shape[0]
+        device = X.device
+        row_batch = 8192  # bound per-launch runtime
+        depth = self._tree_depth() if self.trees else 0
+        if not X.val.is_cuda or depth >= 32:
+            Xc = X.to("cpu")
+            res = np.zeros((n, K, U + 1), dtype=np.float64)
+            for s0 in range(0, n if self.trees else 0, row_batch):
+                res[s0:s0 + row_batch] = self._contrib_used_columns(
+                    Xc, s0, min(n, s0 + row_batch))
+            res[:, :, U] = self.expected_value()[None, :K]
+            return feats, torch.from_numpy(res.astype(np.float32)).to(device)
+        expected = torch.from_numpy(
+            self.expected_value().astype(np.float32)).to(device)
+        values = torch.zeros(n, K, U + 1, dtype=torch.float32, device=device)
+        if self.trees and n:
+            f = self._flat(device)
+            sf = self._shap_flat(device)
+            for s0 in range(0, n, row_batch):
+                e0 = min(n, s0 + row_batch)
+                values[s0:e0] = backend.tree_shap_csr(
+                    f["feature"], f["threshold"], f["left"], f["right"],
+                    sf["value"], sf["count"], f["offsets"], sf["slot"], U,
+                    X.indptr, X.col, X.val, X.shape[1], K, depth,
+                    row_begin=s0, row_end=e0, max_blocks=max_blocks,
+                    cat_offset=f.get("cat_offset"),
+                    cat_words=f.get("cat_words"))
+        values[:, :, U] = expected[:K].unsqueeze(0)
+        return feats, values
+
+    def _contrib_used_columns(self, X, s0, e0) -> np.ndarray:
+        """CPU TreeSHAP of CSR rows [s0, e0): (rows, K, U + 1) float64, the
+        last cell left 0.  Gathers the U used columns into a dense
+        (rows, U) block — forest-sized, not matrix-sized — and runs
+        Tree.shap_values on trees whose split features are renamed to
+        their slots: the dense CPU path's arithmetic, operation for
+        operation."""
+        from ...ops import cpu_ref
+        feats = self.used_features()
+        U, K, m = int(feats.size), self.n_outputs, e0 - s0
+        res = np.zeros((m, K, U + 1), dtype=np.float64)
+        if not U or not m:
+            return res
+        value_of = cpu_ref._csr_value_of(X.indptr, X.col, X.val, X.shape[1])
+        rows = torch.arange(s0, e0).unsqueeze(1).expand(m, U)
+        cols = torch.from_numpy(feats).unsqueeze(0).expand(m, U)
+        Xu = value_of(rows, cols).numpy()
+        if "slot_trees" not in self._flat_cache:
+            self._flat_cache["slot_trees"] = [
+                Tree(np.where(t.feature >= 0,
+                              np.searchsorted(feats, np.maximum(t.feature, 0)),
+                              -1),
+                     t.threshold, t.thr_bin, t.left, t.right, t.value,
+                     t.count, t.gain, t.leaf_index, t.shrinkage,
+                     t.cat_offset, t.cat_words) for t in self.trees]
+        for ti, (t, w) in enumerate(zip(self._flat_cache["slot_trees"],
+                                        self.tree_weights)):
+            res[:, ti % K] += t.shap_values(Xu, scale=float(w))
+        return res
+
     def predict_contrib(self, X: torch.Tensor) -> np.ndarray:
         """TreeSHAP contributions with the expected value last per class:
         (n, n_features+1) for single-output models, (n, K*(n_features+1))
         for multiclass (LightGBM contrib layout).
-        GPU path: tree_shap_k kernel (trees deeper than 32 fall back to CPU)."""
+        GPU path: tree_shap_k kernel (trees deeper than 32 fall back to CPU).
+        A CsrMatrix is explained as CSR (predict_contrib_sparse) and only the
+        result is laid out densely."""
         if hasattr(X, "densify_chunks"):
-            # CsrMatrix: the SHAP output is dense (n, nf+1) by definition, so
-            # densify in the bounded row tiles densify_chunks yields
-            width = self.n_outputs * (self.n_features + 1)
-            outs = [self.predict_contrib(chunk)
-                    for _, chunk in X.densify_chunks()]
-            return (np.concatenate(outs, axis=0) if outs
-                    else np.zeros((0, width), dtype=np.float32))
+            # CsrMatrix: compact contributions scattered into the dense
+            # contract in row tiles; the input is never densified
+            feats, values = self.predict_contrib_sparse(X)
+            K, nf, U = self.n_outputs, self.n_features, int(feats.size)
+            out = np.zeros((X.shape[0], K, nf + 1), dtype=np.float32)
+            for s0 in range(0, X.shape[0], 8192):
+                tile = values[s0:s0 + 8192].cpu().numpy()
+                out[s0:s0 + 8192, :, feats] = tile[:, :, :U]
+                out[s0:s0 + 8192, :, nf] = tile[:, :, U]
+            return out.reshape(-1, K * (nf + 1))
         depth = self._tree_depth() if self.trees else 0
         K = self.n_outputs
         nf = self.n_features

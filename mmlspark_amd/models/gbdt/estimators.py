@@ -115,6 +115,11 @@ class _GBDTParams(Params):
     featuresShapCol = Param("featuresShapCol",
                             "output column for SHAP contributions "
                             "(propagated to the model)", None)
+    featuresShapSparse = Param("featuresShapSparse",
+                               "sparse features: emit featuresShapCol as "
+                               "SparseVectors over the features the forest "
+                               "splits on (propagated to the model)", False,
+                               toBool)
     # Spark/JVM topology params accepted for API compatibility; topology is
     # one-process-per-GPU with RCCL here, so they change nothing (documented
     # in PARITY.md — LightGBMParams.scala:54-100)
@@ -291,7 +296,8 @@ class _GBDTEstimatorBase(_GBDTParams, Estimator):
                 checkpoint_every=self.get("checkpointInterval"))
         model = self._model_class()(booster=booster)
         for p in ("labelCol", "featuresCol", "featureCols", "predictionCol",
-                  "leafPredictionCol", "featuresShapCol"):
+                  "leafPredictionCol", "featuresShapCol",
+                  "featuresShapSparse"):
             model.set(p, self.get(p))
         model._training_stats = stats
         return model
@@ -319,6 +325,10 @@ class _GBDTModelBase(Model):
                               "output column for per-tree leaf indices", None)
     featuresShapCol = Param("featuresShapCol",
                             "output column for SHAP contributions", None)
+    featuresShapSparse = Param("featuresShapSparse",
+                               "sparse features: emit featuresShapCol as "
+                               "SparseVectors over the features the forest "
+                               "splits on", False, toBool)
     boosterModelStr = Param("boosterModelStr", "serialized booster", None,
                             is_complex=True)
     startIteration = Param("startIteration", "first iteration used at "
@@ -421,9 +431,28 @@ class _GBDTModelBase(Model):
             leaves = self.booster.predict_leaf(X).cpu().numpy().astype(np.float64)
             out[self.get("leafPredictionCol")] = matrix_to_vector_column(leaves)
         if self.get("featuresShapCol"):
-            contrib = self.booster.predict_contrib(X)
-            out[self.get("featuresShapCol")] = matrix_to_vector_column(contrib)
+            if self.get("featuresShapSparse") and hasattr(X, "densify_chunks"):
+                out[self.get("featuresShapCol")] = self._sparse_contrib(X)
+            else:
+                contrib = self.booster.predict_contrib(X)
+                out[self.get("featuresShapCol")] = \
+                    matrix_to_vector_column(contrib)
         return out
+
+    def _sparse_contrib(self, X) -> list:
+        """featuresShapCol as one SparseVector per row: size K*(nf+1), the
+        LightGBM contrib layout, storing only the features the forest splits
+        on and the expected value — a per-row size set by the forest, not by
+        the matrix width."""
+        from ...core.schema import SparseVector
+        b = self.booster
+        feats, values = b.predict_contrib_sparse(X)
+        K, nf = b.n_outputs, b.n_features
+        per_class = np.concatenate([feats, [nf]]).astype(np.int64)
+        indices = (np.arange(K, dtype=np.int64)[:, None] * (nf + 1)
+                   + per_class[None, :]).reshape(-1)
+        flat = values.reshape(values.shape[0], -1).cpu().numpy()
+        return [SparseVector(K * (nf + 1), indices, row) for row in flat]
 
 
 @register

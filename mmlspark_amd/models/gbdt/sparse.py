@@ -113,10 +113,10 @@ class CsrMatrix:
                          self.val[a:b], (end - start, self.shape[1]))
 
     def densify(self, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Dense (m, nf) float32 for the selected rows.  Scoring does not
-        use it (Booster.predict_raw / predict_leaf traverse the CSR rows
-        directly); SHAP contributions, whose output is dense anyway, and
-        tests do."""
+        """Dense (m, nf) float32 for the selected rows.  Neither scoring
+        nor SHAP uses it (Booster.predict_raw / predict_leaf /
+        predict_contrib_sparse traverse the CSR rows directly); tests and
+        benchmarks that compare against the dense kernels do."""
         n, nf = self.shape
         if rows is None:
             rows = torch.arange(n, device=self.device)

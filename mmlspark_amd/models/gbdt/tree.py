@@ -44,9 +44,11 @@ class Tree:
         return self.cat_offset[i] >= 0
 
     def cat_goes_left(self, i: int, category: float) -> bool:
+        if np.isnan(category):
+            return True  # missing → left (int(nan) raises)
         b = int(category)
-        if not (0 <= b < 256) or np.isnan(category):
-            return True  # missing/out-of-range → left
+        if not (0 <= b < 256):
+            return True  # out-of-range → left
         w = self.cat_words[self.cat_offset[i] * 8 + (b >> 5)]
         return bool((int(w) >> (b & 31)) & 1)
 

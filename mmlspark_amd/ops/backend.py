@@ -240,6 +240,33 @@ def predict_leaf_csr(node_feature, node_threshold, node_left, node_right,
         tree_offsets, indptr, col, val, n_cols, cat_offset, cat_words)
 
 
+def tree_shap_csr(node_feature, node_threshold, node_left, node_right,
+                  node_value, node_count, tree_offsets, node_slot, n_slots,
+                  indptr, col, val, n_cols, n_outputs, max_depth,
+                  row_begin=0, row_end=None, max_blocks=0, cat_offset=None,
+                  cat_words=None):
+    """TreeSHAP over the CSR rows [row_begin, row_end) — compact float32
+    (rows, n_outputs, n_slots + 1): one cell per distinct split feature
+    (node_slot maps an interior node to it), the last cell left 0 for the
+    expected value.  node_value holds the leaf values already folded with
+    the tree weights, node_count the float32 covers.  max_depth (< 32)
+    picks the kernel's depth template; max_blocks > 0 overrides its grid
+    policy."""
+    if row_end is None:
+        row_end = indptr.numel() - 1
+    if val.is_cuda:
+        return _require_ext().tree_shap_csr(
+            node_feature, node_threshold, node_left, node_right, node_value,
+            node_count, tree_offsets, node_slot, n_slots, indptr, col, val,
+            n_outputs, max_depth, row_begin, row_end, max_blocks, cat_offset,
+            cat_words)
+    return cpu_ref.tree_shap_csr(
+        node_feature, node_threshold, node_left, node_right, node_value,
+        node_count, tree_offsets, node_slot, n_slots, indptr, col, val,
+        n_cols, n_outputs, row_begin, row_end, cat_offset,
+        cat_words).to(torch.float32)
+
+
 # ------------------------------------------------------------------- images
 JPEG_MAX_PIXELS = 1 << 26
 

@@ -207,6 +207,127 @@ def predict_leaf_csr(node_feature, node_threshold, node_left, node_right,
     return node_leaf_index[idx].to(torch.int32)
 
 
+def tree_shap_csr(node_feature, node_threshold, node_left, node_right,
+                  node_value, node_count, tree_offsets, node_slot, n_slots,
+                  indptr, col, val, n_cols, n_outputs, row_begin=0,
+                  row_end=None, cat_offset=None, cat_words=None,
+                  return_bound=False):
+    """Path-dependent TreeSHAP over the CSR rows [row_begin, row_end), compact
+    result: (rows, n_outputs, n_slots + 1) float64, one cell per distinct
+    split feature (node_slot[node] = its index in the sorted used-feature
+    list) and a last cell left 0 for the expected value.
+
+    The float64 oracle of tree_shap_csr_k and the CPU implementation.  It
+    takes the kernel's own flat float32 arrays (leaf values already folded
+    with shrinkage and tree weight, float32 covers), reads row values through
+    _csr_value_of, branches with _go_left (the kernels' rule) and forms each
+    cover ratio as a float32 division; everything after that is float64.
+
+    The DFS order of a tree does not depend on the row — only the
+    one-fractions do — so each tree is walked once with (rows,) vectors.
+
+    return_bound=True also returns, per output cell, N (leaf terms added
+    into the cell) and S = sum |leaf value| * unwound_sum, the addends'
+    magnitude without their (o - z) factor."""
+    import numpy as np
+    n_all = indptr.numel() - 1
+    row_end = n_all if row_end is None else int(row_end)
+    row_begin = int(row_begin)
+    n = row_end - row_begin
+    n_trees = tree_offsets.numel() - 1
+    phi = np.zeros((n, n_outputs, n_slots + 1), dtype=np.float64)
+    N = np.zeros(phi.shape, dtype=np.int64)
+    S = np.zeros(phi.shape, dtype=np.float64)
+
+    def result():
+        out = torch.from_numpy(phi)
+        if return_bound:
+            return out, torch.from_numpy(N), torch.from_numpy(S)
+        return out
+
+    if n <= 0 or n_trees <= 0:
+        return result()
+
+    value_of = _csr_value_of(indptr, col, val, n_cols)
+    all_rows = torch.arange(row_begin, row_end).unsqueeze(1)
+
+    def branch_decisions(lo, hi):
+        """{node: (rows,) float64 1.0 where the row goes left} for one
+        tree's interior nodes, from one vectorised lookup."""
+        interior = lo + torch.nonzero(node_feature[lo:hi] >= 0).view(-1)
+        if not interior.numel():
+            return {}
+        idx = interior.unsqueeze(0).expand(n, interior.numel())
+        xv = value_of(all_rows.expand(n, interior.numel()),
+                      node_feature[idx].long())
+        gl = _go_left(xv, idx, node_threshold, cat_offset,
+                      cat_words).numpy().astype(np.float64)
+        return {int(nd): gl[:, j] for j, nd in enumerate(interior.tolist())}
+
+    feat = node_feature.numpy()
+    left, right = node_left.numpy(), node_right.numpy()
+    value = node_value.numpy().astype(np.float32)
+    cnt = node_count.numpy().astype(np.float32)
+    slot = node_slot.numpy()
+    offsets = tree_offsets.numpy()
+    tiny = np.float32(1e-12)
+
+    def leaf(nd, k, path):
+        # merge duplicate slots: z is a scalar, o a (rows,) 0/1 vector
+        ms, mz, mo = [], [], []
+        for s_, z_, o_ in path:
+            if s_ in ms:
+                j = ms.index(s_)
+                mz[j] = mz[j] * z_
+                mo[j] = mo[j] * o_
+            else:
+                ms.append(s_)
+                mz.append(z_)
+                mo.append(o_)
+        m = len(ms)
+        w = [np.ones(n)] + [None] * m
+        for e in range(m):
+            w[e + 1] = np.zeros(n)
+            for i in range(e, -1, -1):
+                w[i + 1] = w[i + 1] + mo[e] * w[i] * (i + 1) / (e + 2)
+                w[i] = mz[e] * w[i] * (e + 1 - i) / (e + 2)
+        leaf_v = float(value[nd])
+        for i in range(m):
+            on = mo[i] != 0.0
+            safe_o = np.where(on, mo[i], 1.0)
+            t_on = np.zeros(n)
+            t_off = np.zeros(n)
+            nrun = w[m]
+            for j in range(m - 1, -1, -1):
+                tmp = nrun * (m + 1) / ((j + 1) * safe_o)
+                t_on = t_on + tmp
+                nrun = w[j] - tmp * mz[i] * (m - j) / (m + 1)
+                t_off = t_off + w[j] * (m + 1) / (mz[i] * (m - j))
+            total = np.where(on, t_on, t_off)
+            phi[:, k, ms[i]] += total * (mo[i] - mz[i]) * leaf_v
+            N[:, k, ms[i]] += 1
+            S[:, k, ms[i]] += abs(leaf_v) * np.abs(total)
+
+    def walk(nd, base, k, path, go_left):
+        if feat[nd] < 0:
+            leaf(nd, k, path)
+            return
+        gl = go_left[nd]
+        denom = np.maximum(cnt[nd], tiny)
+        for child, one in ((left[nd], gl), (right[nd], 1.0 - gl)):
+            c = base + int(child)
+            z = float(np.float32(cnt[c]) / denom)  # the kernel's f32 ratio
+            walk(c, base, k, path + [(int(slot[nd]), z, one)], go_left)
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for t in range(n_trees):
+            base, end = int(offsets[t]), int(offsets[t + 1])
+            if end > base:
+                walk(base, base, t % n_outputs, [],
+                     branch_decisions(base, end))
+    return result()
+
+
 def bin_matrix(X: torch.Tensor, upper_bounds: torch.Tensor,
                n_bins: int) -> torch.Tensor:
     """Quantile-bin a dense (n, nf) matrix into the (ngroups, n, 4) i4 layout.

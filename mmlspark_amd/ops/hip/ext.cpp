@@ -50,6 +50,11 @@ void launch_tree_shap(const int*, const float*, const int*, const int*,
                       const float*, const float*, const long*, const int*,
                       const unsigned*, const float*, long, int, int, int, int,
                       float*, hipStream_t);
+void launch_tree_shap_csr(const int*, const float*, const int*, const int*,
+                          const float*, const float*, const long*, const int*,
+                          const int*, const unsigned*, const long*, const int*,
+                          const float*, long, long, int, int, int, int, float*,
+                          long, hipStream_t);
 void launch_csr_hist_fixed(const long*, const int*,
                            const unsigned char*, const long long*,
                            const long long*, const int*, long, long long*,
@@ -376,6 +381,50 @@ torch::Tensor tree_shap(torch::Tensor feat, torch::Tensor thr,
   return out;
 }
 
+// TreeSHAP over the CSR row window [row_begin, row_end) of the full indptr;
+// compact result (rows, n_outputs, n_slots + 1), slot n_slots (the expected
+// value) left zero for the caller.
+torch::Tensor tree_shap_csr(torch::Tensor feat, torch::Tensor thr,
+                            torch::Tensor left, torch::Tensor right,
+                            torch::Tensor val, torch::Tensor cnt,
+                            torch::Tensor offsets, torch::Tensor slot,
+                            long n_slots, torch::Tensor indptr,
+                            torch::Tensor col, torch::Tensor xval,
+                            long n_outputs, long max_depth, long row_begin,
+                            long row_end, long max_blocks,
+                            c10::optional<torch::Tensor> cat_offset,
+                            c10::optional<torch::Tensor> cat_words) {
+  const long n = check_csr_rows(indptr, col, xval);
+  CHECK_DEV(feat); CHECK_CONTIG(feat);
+  CHECK_DEV(offsets); CHECK_CONTIG(offsets);
+  CHECK_DEV(slot); CHECK_CONTIG(slot);
+  CHECK_DEV(cnt); CHECK_CONTIG(cnt);
+  TORCH_CHECK(offsets.dtype() == torch::kInt64, "offsets must be int64");
+  TORCH_CHECK(slot.dtype() == torch::kInt32, "slot must be int32");
+  TORCH_CHECK(slot.numel() == feat.numel() && cnt.numel() == feat.numel()
+                  && val.numel() == feat.numel(),
+              "slot, cnt and val must have one entry per node");
+  TORCH_CHECK(n_outputs >= 1, "n_outputs must be positive");
+  TORCH_CHECK(n_slots >= 0, "n_slots must not be negative");
+  TORCH_CHECK(0 <= row_begin && row_begin <= row_end && row_end <= n,
+              "row window outside the matrix");
+  TORCH_CHECK(max_blocks >= 0, "max_blocks must not be negative");
+  TORCH_CHECK(max_depth < 32, "trees of depth >= 32 need the CPU reference");
+  const long n_trees = offsets.numel() - 1;
+  auto out = torch::zeros({row_end - row_begin, n_outputs, n_slots + 1},
+                          xval.options().dtype(torch::kFloat32));
+  if (row_end == row_begin || n_trees <= 0) return out;
+  auto [co, cw] = cat_ptrs(cat_offset, cat_words);
+  launch_tree_shap_csr(
+      feat.data_ptr<int>(), thr.data_ptr<float>(), left.data_ptr<int>(),
+      right.data_ptr<int>(), val.data_ptr<float>(), cnt.data_ptr<float>(),
+      offsets.data_ptr<long>(), slot.data_ptr<int>(), co, cw,
+      indptr.data_ptr<long>(), col.data_ptr<int>(), xval.data_ptr<float>(),
+      row_begin, row_end, (int)n_trees, (int)n_outputs, (int)n_slots,
+      (int)max_depth, out.data_ptr<float>(), max_blocks, cur_stream());
+  return out;
+}
+
 // --------------------------------------------------------------- sparse CSR
 torch::Tensor csr_hist_fixed(torch::Tensor indptr, torch::Tensor col,
                              torch::Tensor binv, torch::Tensor gq,
@@ -544,6 +593,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vw_sgd_minibatch", &vw_sgd_minibatch, "adaptive sparse SGD minibatch");
   m.def("vw_predict", &vw_predict, "sparse linear predict");
   m.def("tree_shap", &tree_shap, "path-dependent TreeSHAP contributions");
+  m.def("tree_shap_csr", &tree_shap_csr,
+        "TreeSHAP over CSR rows, compact per-used-feature contributions");
   m.def("csr_hist_fixed", &csr_hist_fixed,
         "fixed-point histogram over stored CSR entries");
   m.def("csr_gather_bins", &csr_gather_bins,

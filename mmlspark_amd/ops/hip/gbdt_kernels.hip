@@ -1897,6 +1897,171 @@ extern "C" void launch_tree_shap(const int* feat, const float* thr,
 #undef TSLAUNCH
 }
 
+// ---------------------------------------------------- tree SHAP, CSR rows
+// tree_shap_k over CSR rows with a COMPACT result: out is
+// (row_end - row_begin, n_outputs, n_slots + 1), one cell per distinct split
+// feature of the forest (slot[node] = index of the node's feature in the
+// sorted used-feature list, host-built) plus the expected value the host
+// fills in.  A tree only credits features it splits on, so nothing of the
+// matrix width is ever allocated.  Same thread = (row, tree) DFS, same f64
+// path weights and f32 cover ratios as tree_shap_k, so both kernels produce
+// the same addends; the differences are
+//   * x[ft] is a binary search in the row's segment (absent = 0.0f, stored
+//     values read as themselves), so the branch is decided once, in phase 0,
+//     and kept in bit 2 of phase[] for the second descent;
+//   * the path carries slots, not feature ids: merging duplicates by slot is
+//     merging by feature, and the leaf credits phi[slot] without a search;
+//   * pairs are tree-major (consecutive lanes = consecutive rows of ONE
+//     tree) and the DFS always takes the left child first, the row's branch
+//     only setting the one-fractions.  The node sequence, the path length
+//     and the duplicate pattern then depend on the tree alone, so a wave
+//     walks one tree in lockstep (node loads are wave-uniform, only the
+//     o == 0 unwind branch diverges) and its 64 atomics go to 64 different
+//     rows.  Row-major pairs with the hot child first, tree_shap_k's
+//     order, took 94.9 ms where this takes 22.5 (8192 rows, 100 trees x 63
+//     leaves, 100 columns; 117.4 -> 26.6 at 100,000 columns;
+//     profiles/csr_shap_variants.txt has each change alone).
+template <int TS_MAXD>
+__global__ void tree_shap_csr_k(const int* __restrict__ feat,
+                                const float* __restrict__ thr,
+                                const int* __restrict__ left,
+                                const int* __restrict__ right,
+                                const float* __restrict__ val,  // leaf values ×w
+                                const float* __restrict__ cnt,
+                                const long* __restrict__ offsets,
+                                const int* __restrict__ slot,
+                                const int* __restrict__ catoff,
+                                const unsigned* __restrict__ catw,
+                                const long* __restrict__ indptr,
+                                const int* __restrict__ col,
+                                const float* __restrict__ xval,
+                                long row_begin, long n, int n_trees,
+                                int n_outputs, int n_slots,
+                                float* __restrict__ out) {
+  const long pair0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long n_pairs = n * (long)n_trees;
+
+  int ps[TS_MAXD + 2];
+  float pz[TS_MAXD + 2], po[TS_MAXD + 2];
+  int ms[TS_MAXD + 2];
+  double mz[TS_MAXD + 2], mo[TS_MAXD + 2], w[TS_MAXD + 2];
+  int nstack[TS_MAXD + 2];
+  signed char phase[TS_MAXD + 2];  // bits 0-1: phase, bit 2: row goes left
+
+  for (long pair = pair0; pair < n_pairs; pair += stride) {
+    const long r = pair % n;  // row within the window
+    const int t = (int)(pair / n);
+    const long base = offsets[t];
+    const long lo = indptr[row_begin + r], hi = indptr[row_begin + r + 1];
+    float* phi = out + (r * n_outputs + (t % n_outputs)) * (n_slots + 1);
+
+    int sp = 0;
+    nstack[0] = (int)base;
+    phase[0] = 0;
+    while (sp >= 0) {
+      const int nd = nstack[sp];
+      const int ph = phase[sp] & 3;
+      if (ph == 0) {
+        const int ft = feat[nd];
+        if (ft < 0) {  // ---- leaf: merge path, extend once, credit slots
+          int m = 0;
+          for (int i = 0; i < sp; ++i) {
+            int k = -1;
+            for (int j = 0; j < m; ++j)
+              if (ms[j] == ps[i]) { k = j; break; }
+            if (k >= 0) { mz[k] *= pz[i]; mo[k] *= po[i]; }
+            else { ms[m] = ps[i]; mz[m] = pz[i]; mo[m] = po[i]; ++m; }
+          }
+          w[0] = 1.0;
+          for (int e = 0; e < m; ++e) {
+            w[e + 1] = 0.0;
+            for (int i = e; i >= 0; --i) {
+              w[i + 1] += mo[e] * w[i] * (double)(i + 1) / (double)(e + 2);
+              w[i] = mz[e] * w[i] * (double)(e + 1 - i) / (double)(e + 2);
+            }
+          }
+          const double leaf_v = val[nd];
+          for (int i = 0; i < m; ++i) {
+            double total = 0.0;
+            double nrun = w[m];
+            if (mo[i] != 0.0) {
+              for (int j = m - 1; j >= 0; --j) {
+                const double tmp =
+                    nrun * (double)(m + 1) / ((double)(j + 1) * mo[i]);
+                total += tmp;
+                nrun = w[j] - tmp * mz[i] * (double)(m - j) / (double)(m + 1);
+              }
+            } else {
+              for (int j = m - 1; j >= 0; --j)
+                total += w[j] * (double)(m + 1) / (mz[i] * (double)(m - j));
+            }
+            atomicAdd(&phi[ms[i]],
+                      (float)(total * (mo[i] - mz[i]) * leaf_v));
+          }
+          --sp;
+          continue;
+        }
+        // interior: one lookup decides both one-fractions; left child first
+        const float xv = csr_row_value(col, xval, lo, hi, ft);
+        const bool gl = go_left_node(xv, nd, thr, catoff, catw);
+        phase[sp] = (signed char)(1 | (gl ? 4 : 0));
+        const int lc = (int)base + left[nd];
+        if (sp < TS_MAXD) {
+          ps[sp] = slot[nd];
+          pz[sp] = cnt[lc] / fmaxf(cnt[nd], 1e-12f);
+          po[sp] = gl ? 1.0f : 0.0f;
+          nstack[sp + 1] = lc;
+          phase[sp + 1] = 0;
+          ++sp;
+        }
+        continue;
+      }
+      if (ph == 1) {  // descend right child
+        const bool gl = (phase[sp] & 4) != 0;
+        phase[sp] = 2;
+        const int rc = (int)base + right[nd];
+        if (sp < TS_MAXD) {
+          pz[sp] = cnt[rc] / fmaxf(cnt[nd], 1e-12f);  // ps[sp] still holds
+          po[sp] = gl ? 0.0f : 1.0f;
+          nstack[sp + 1] = rc;
+          phase[sp + 1] = 0;
+          ++sp;
+        }
+        continue;
+      }
+      --sp;
+    }
+  }
+}
+
+// Row window [row_begin, row_end) of the full indptr; out holds the window's
+// rows only.  max_blocks = 0: the policy (tree_shap_k's 8192-block cap); a
+// positive value overrides it.
+extern "C" void launch_tree_shap_csr(
+    const int* feat, const float* thr, const int* left, const int* right,
+    const float* val, const float* cnt, const long* offsets, const int* slot,
+    const int* catoff, const unsigned* catw, const long* indptr,
+    const int* col, const float* xval, long row_begin, long row_end,
+    int n_trees, int n_outputs, int n_slots, int max_depth, float* out,
+    long max_blocks, hipStream_t stream) {
+  const long n = row_end - row_begin;
+  if (n <= 0 || n_trees <= 0) return;
+  const long pairs = n * (long)n_trees;
+  long blocks = (pairs + 255) / 256;
+  const long cap = max_blocks > 0 ? max_blocks : 8192;
+  if (blocks > cap) blocks = cap;
+#define TSLAUNCH(D)                                                        \
+  hipLaunchKernelGGL((tree_shap_csr_k<D>), dim3((unsigned)blocks),         \
+                     dim3(256), 0, stream, feat, thr, left, right, val,    \
+                     cnt, offsets, slot, catoff, catw, indptr, col, xval,  \
+                     row_begin, n, n_trees, n_outputs, n_slots, out)
+  if (max_depth < 8) TSLAUNCH(8);
+  else if (max_depth < 16) TSLAUNCH(16);
+  else TSLAUNCH(32);
+#undef TSLAUNCH
+}
+
 // -------------------------------------------------------------- sparse CSR
 // Histogram over STORED entries only (the reference's CSR ingestion,
 // DatasetAggregator.scala:442); implicit zeros are corrected host-side by
