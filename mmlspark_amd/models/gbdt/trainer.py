@@ -366,7 +366,7 @@ class TreeGrower:
         self.stats.partition_s += time.perf_counter() - t0
         return rows_l, rows_r
 
-    def _grow_native(self, rows_root, grad, hess, feat_mask):
+    def _grow_native(self, rows_root, grad, hess, feat_mask, update=None):
         """Whole leaf-wise loop in the C++ driver (ops/hip/gbdt_grower.cpp)
         — one Python call per tree instead of ~6 per split."""
         from ...ops import _hip_grower
@@ -387,6 +387,11 @@ class TreeGrower:
             num_mask[self.cat_features] = False
         cats_t = (torch.tensor(cats_active, dtype=torch.int64)
                   if cats_active else None)
+        # the session's own arange: every row, in order, so the root can read
+        # the static bin planes in place (bagging, GOSS and rf pass a subset)
+        identity = (self.identity_rows is not None
+                    and rows_root is self.identity_rows)
+        preds_col, shrinkage = update if update is not None else (None, 1.0)
         t0 = time.perf_counter()
         d = _hip_grower.grow_tree_native(
             self.binned, self.binned_pair, rows_root.contiguous(), grad, hess,
@@ -396,14 +401,24 @@ class TreeGrower:
             cfg.min_gain_to_split, cfg.max_delta_step, cfg.num_leaves,
             cfg.max_depth, num_mask, cats_t, self.cat_smooth, pg,
             self.comm.is_distributed or bool(os.environ.get(
-                "MMLSPARK_AMD_FORCE_DIST_GROWER")))
+                "MMLSPARK_AMD_FORCE_DIST_GROWER")),
+            rows_identity=identity, preds_col=preds_col, shrinkage=shrinkage)
         self.stats.hist_s += time.perf_counter() - t0
         feature = d["feature"].numpy()
         thr_bin = d["thr_bin"].numpy()
         cat_offset = d["cat_offset"].numpy()
+        # thresholds from a host copy of the bin bounds, fetched once per
+        # grower: BinMapper.bin_upper_value reads the device tensor, one
+        # blocking 4-byte copy per split with the GPU idle meanwhile
+        if self._upper_bounds_host is None:
+            self._upper_bounds_host = \
+                self.bin_mapper.upper_bounds.detach().cpu().numpy()
+        ub = self._upper_bounds_host
+        last_bin = self.bin_mapper.n_bins - 1
         threshold = np.array(
             [float("nan") if cat_offset[i] >= 0 else
-             self.bin_mapper.bin_upper_value(int(f), int(b)) if f >= 0 else 0.0
+             (float("inf") if b >= last_bin else float(ub[f, b]))
+             if f >= 0 else 0.0
              for i, (f, b) in enumerate(zip(feature, thr_bin))],
             dtype=np.float32)
         tree = Tree(feature, threshold, thr_bin, d["left"].numpy(),
@@ -412,30 +427,42 @@ class TreeGrower:
                     d["leaf_index"].numpy(), shrinkage=1.0,
                     cat_offset=cat_offset,
                     cat_words=d["cat_words"].numpy().view(np.uint32))
-        offs = d["leaf_offsets"].tolist()
         nodes = d["leaf_nodes"].tolist()
-        leaves = []
-        for i, nid in enumerate(nodes):
-            lf = _Leaf(int(nid), d["leaf_rows"][offs[i]:offs[i + 1]], None,
-                       0, 0, 0, 0)
-            leaves.append(lf)
-        # concatenated leaf rows as the native prediction update takes them
+        # concatenated leaf rows as the native prediction update takes them,
+        # and whether the grower has already applied that update
         self.native_leaves = (d["leaf_rows"], d["leaf_offsets"], nodes)
-        return tree, leaves
+        self.native_applied = bool(int(d["preds_applied"][0]))
+        # per-leaf row slices are cut only where something reads them
+        return tree, None
+
+    def native_leaf_list(self):
+        """The native grower's leaves as _Leaf objects (one row slice each)."""
+        leaf_rows, leaf_offsets, nodes = self.native_leaves
+        offs = leaf_offsets.tolist()
+        return [_Leaf(int(nid), leaf_rows[offs[i]:offs[i + 1]], None,
+                      0, 0, 0, 0) for i, nid in enumerate(nodes)]
 
     native_ok = True  # sparse grower overrides (no arena path yet)
     native_leaves = None  # set by the native grower for the tree just grown
+    native_applied = False  # the native grower updated the predictions itself
+    identity_rows = None  # the session's arange over all rows, if it has one
+    _upper_bounds_host = None  # numpy copy of bin_mapper.upper_bounds
 
     def grow(self, rows_root: torch.Tensor, grad: torch.Tensor,
-             hess: torch.Tensor, feat_mask) -> (Tree, List):
+             hess: torch.Tensor, feat_mask, update=None) -> (Tree, List):
+        """update: (preds column, shrinkage) if the native grower may add the
+        new tree's leaf values to the predictions itself; whether it did is
+        left in native_applied."""
         self.native_leaves = None
+        self.native_applied = False
         if (self.native_ok and self.fixed and not self.voting
                 and not os.environ.get(
                     "MMLSPARK_AMD_NO_NATIVE_GROWER")):
             try:
                 from ...ops import _hip_grower  # noqa: F401
                 self.set_scales(grad, hess)
-                return self._grow_native(rows_root, grad, hess, feat_mask)
+                return self._grow_native(rows_root, grad, hess, feat_mask,
+                                         update)
             except ImportError:
                 pass
         cfg = self.cfg
@@ -758,6 +785,7 @@ class TrainingSession:
                                  self.bin_mapper, n_global=n_global)
         self.gen = torch.Generator(device="cpu")
         self.all_rows = torch.arange(n, dtype=torch.int32, device=device)
+        self.grower.identity_rows = self.all_rows
         self.n_start_trees = len(self.trees)
         self.it = 0
 
@@ -868,16 +896,26 @@ class TrainingSession:
         # ---- one tree per output class --------------------------------------
         new_trees = []
         for k in range(K):
-            tree, leaves = self.grower.grow(rows_root, grad[:, k].contiguous(),
-                                            hess[:, k].contiguous(), feat_mask)
+            # the native grower adds the new tree to the predictions itself,
+            # right behind its last kernel, wherever the one-kernel update
+            # below would be taken
+            fused = (not rf_mode and not dropped and preds.is_cuda
+                     and preds.dtype == torch.float32)
+            tree, leaves = self.grower.grow(
+                rows_root, grad[:, k].contiguous(), hess[:, k].contiguous(),
+                feat_mask,
+                update=(preds[:, k], cfg.learning_rate) if fused else None)
             tree.shrinkage = 1.0 if rf_mode else cfg.learning_rate
             if not rf_mode:
                 # one fused update: concat leaf row lists + repeat leaf values
                 t0 = time.perf_counter()
-                live = [lf for lf in leaves if lf.rows.numel()]
                 native = self.grower.native_leaves
-                if (native is not None and not dropped
-                        and preds.is_cuda and preds.dtype == torch.float32):
+                if leaves is None and not (native is not None and fused):
+                    leaves = self.grower.native_leaf_list()
+                live = [lf for lf in leaves or () if lf.rows.numel()]
+                if self.grower.native_applied:
+                    pass  # already in preds[:, k]
+                elif native is not None and fused:
                     from ...ops import _hip_grower
                     leaf_rows, leaf_offsets, nodes = native
                     vals = torch.tensor(

@@ -11,7 +11,10 @@
 //    tools/hist_gather_probe.py) is gone; the cost is streaming ~124 B/row
 //    of arena payload per split, which HBM3E absorbs.  Live leaves always
 //    own disjoint row ranges, so two in-flight splits never overlap even
-//    across buffers.
+//    across buffers.  When the root row set is every row in order (no
+//    bagging, no GOSS), the root reads its planes straight from the static
+//    binned_pair — a third, read-only source — and only the gradient records
+//    and row ids of buffer 0 are written per tree.
 //
 //  * SPECULATION: a popped leaf's split work is independent of processing
 //    order (its split was fixed at creation), so the driver pre-launches the
@@ -108,6 +111,16 @@ int grower_streams_from_env() {
   return (int)v;
 }
 
+// On/off switches of the tree's head and tail (docs/kernels.md); all default
+// to on.  Read once per tree, before any launch.
+bool grower_switch(const char* name) {
+  const char* e = std::getenv(name);
+  if (!e || !*e) return true;
+  TORCH_CHECK((e[0] == '0' || e[0] == '1') && e[1] == '\0', name,
+              " must be 0 or 1, got '", e, "'");
+  return e[0] == '1';
+}
+
 // Block width, block order and LDS layout of the range histogram.  An
 // explicit argument wins; else MMLSPARK_AMD_HIST_THREADS (0/256/512/1024),
 // MMLSPARK_AMD_HIST_ORDER (0/1) and MMLSPARK_AMD_HIST_LAYOUT (0/1/2); else
@@ -153,6 +166,9 @@ struct GrowCtx {
   int tail_bytes;  // valid feature-bytes in the last pair (zero-pad skipped)
   // double-buffered arena: [0]/[1]
   torch::Tensor pair[2];   // (npairs, n_arena) i64 paired bin planes
+  // kRootBuf's planes: the static binned_pair when the root reads it in
+  // place (never a scatter destination), else null
+  const void* root_pair = nullptr;
   torch::Tensor ghq[2];    // (n_arena, 2) i64 (gq, CNT|hq)
   torch::Tensor rowid[2];  // (n_arena,) i32 original row ids
   long nf;
@@ -186,6 +202,17 @@ struct GrowCtx {
   long slab_used_zero = 0, slab_used_raw = 0;
 };
 
+// LeafCand::buf of a root that reads the static planes.  Its gradient records
+// and row ids are buffer 0's and its children go to buffer 1, so buffer 0's
+// planes are first written by the root's grandchildren.
+constexpr int kRootBuf = 2;
+
+const void* pair_of(const GrowCtx& ctx, int buf) {
+  return buf == kRootBuf ? ctx.root_pair : ctx.pair[buf].data_ptr();
+}
+int small_buf(int buf) { return buf == kRootBuf ? 0 : buf; }  // ghq, rowid
+int child_buf(int buf) { return buf == kRootBuf ? 1 : buf ^ 1; }
+
 struct SplitJob {
   torch::Tensor hist_l, hist_r;
   torch::Tensor scan_host;  // (nh, nf_pad, 6) f32 pinned per-feature records
@@ -193,6 +220,7 @@ struct SplitJob {
   torch::Tensor cat_host;   // (nh, ncat, nb, 3) i64 pinned — cat hist rows
   torch::Tensor bits_host;  // (8,) i32 pinned — partition bitset staging
   torch::Tensor bits_dev;   // (8,) i32 device
+  torch::Tensor row0_host;  // (nb, 3) i64 pinned — root: feature 0's hist row
   long nl_known = -1;       // host-known left count (single-rank fast path)
   hipEvent_t ev = nullptr;
 
@@ -214,7 +242,8 @@ struct LeafCand {
   int node_id = 0;
   int depth = 0;
   long lo = 0, hi = 0;  // arena row range
-  int buf = 0;          // which arena buffer holds this leaf's rows
+  int buf = 0;          // which arena buffer holds this leaf's rows (0, 1
+                        // or kRootBuf)
   torch::Tensor hist;   // int64 (nf_pad, nb, 3), globally reduced
   double G = 0, H = 0, C = 0;
   double GL = 0, HL = 0, CL = 0;
@@ -249,7 +278,7 @@ torch::Tensor build_hist(GrowCtx& ctx, int buf, long lo, long m,
                          const int* nl_dev = nullptr, int side = -1) {
   auto hist = hist_slot(ctx, true);
   launch_hist_pair_range(
-      ctx.pair[buf].data_ptr(), ctx.ghq[buf].data_ptr(), ctx.n_arena, lo, m,
+      pair_of(ctx, buf), ctx.ghq[small_buf(buf)].data_ptr(), ctx.n_arena, lo, m,
       (long long*)hist.data_ptr<int64_t>(), ctx.n_bins, ctx.npairs,
       ctx.tail_bytes, nl_dev, side, 0, hist_threads(), hist_order(),
       hist_layout(), grower_stream());
@@ -262,10 +291,11 @@ torch::Tensor build_hist(GrowCtx& ctx, int buf, long lo, long m,
 
 // launch the fused sibling subtract + scan (parent undefined: scan `small`
 // alone, the root); the per-feature records land in a pinned host buffer
-// behind an event — no stream sync, the arg-max over features is the host's
+// behind an event — no stream sync, the arg-max over features is the host's.
+// row0: feature 0's row of `small` rides back too (the root's totals).
 void launch_scan_async(GrowCtx& ctx, const torch::Tensor& parent,
                        const torch::Tensor& small, torch::Tensor big,
-                       bool small_is_left, SplitJob& job) {
+                       bool small_is_left, SplitJob& job, bool row0 = false) {
   const long nh = parent.defined() ? 2 : 1;
   const long nf_pad = small.size(0);
   auto records = torch::empty(
@@ -306,6 +336,15 @@ void launch_scan_async(GrowCtx& ctx, const torch::Tensor& parent,
                            per_hist * sizeof(int64_t), hipMemcpyDeviceToHost,
                            grower_stream());
     }
+  }
+  if (row0) {
+    job.row0_host = torch::empty({(long)ctx.n_bins, 3}, torch::TensorOptions()
+                                                            .dtype(torch::kInt64)
+                                                            .pinned_memory(true));
+    (void)hipMemcpyAsync(job.row0_host.data_ptr<int64_t>(),
+                         small.data_ptr<int64_t>(),
+                         (size_t)ctx.n_bins * 3 * sizeof(int64_t),
+                         hipMemcpyDeviceToHost, grower_stream());
   }
   (void)hipEventCreateWithFlags(&job.ev, hipEventDisableTiming);
   (void)hipEventRecord(job.ev, grower_stream());
@@ -413,8 +452,12 @@ void resolve_best(const GrowCtx& ctx, SplitJob& job, int hi, LeafCand& c) {
 // No device-side wait orders it after other chains, and none is needed: a
 // chain is launched only for a leaf whose creating chain's event the host
 // has already waited on (the root: the root scan's event, which also covers
-// the arena setup), and live leaves own disjoint arena ranges.  Keep that
-// invariant when changing the loop below.
+// the arena setup), and live leaves own disjoint arena ranges.  That holds
+// for a root on the static planes too: its chain reads binned_pair and
+// buffer 0's records and row ids over [0, n) and writes buffer 1; buffer 0
+// is written again only by chains of the root's children, which start after
+// the root chain's event, and binned_pair is never a destination (child_buf
+// never returns kRootBuf).  Keep that invariant when changing the loop below.
 void launch_job(GrowCtx& ctx, LeafCand& leaf) {
   const size_t si = ctx.next_stream;
   ctx.next_stream = (ctx.next_stream + 1) % ctx.streams.size();
@@ -424,7 +467,7 @@ void launch_job(GrowCtx& ctx, LeafCand& leaf) {
   int* const total = ctx.total[si].data_ptr<int>();
   auto job = std::make_shared<SplitJob>();
   const long m = leaf.hi - leaf.lo;
-  const int src = leaf.buf, dst = leaf.buf ^ 1;
+  const int src = leaf.buf, dst = child_buf(leaf.buf);
   const unsigned* cat_bits = nullptr;
   if (!leaf.cats.empty()) {
     // categorical split: stage the 256-bit category set and partition by
@@ -442,8 +485,8 @@ void launch_job(GrowCtx& ctx, LeafCand& leaf) {
     cat_bits = (const unsigned*)job->bits_dev.data_ptr<int>();
   }
   launch_partition_arena(
-      ctx.pair[src].data_ptr(), ctx.ghq[src].data_ptr(),
-      ctx.rowid[src].data_ptr<int>(), ctx.pair[dst].data_ptr(),
+      pair_of(ctx, src), ctx.ghq[small_buf(src)].data_ptr(),
+      ctx.rowid[small_buf(src)].data_ptr<int>(), ctx.pair[dst].data_ptr(),
       ctx.ghq[dst].data_ptr(), ctx.rowid[dst].data_ptr<int>(), ctx.n_arena,
       ctx.npairs, leaf.lo, m, leaf.feat, leaf.bin, cat_bits,
       scratch, total, 0, 0, grower_stream());
@@ -491,7 +534,10 @@ bool splittable(const GrowCtx& ctx, const LeafCand& c) {
 }  // namespace
 
 // Returns dict with node arrays (CPU int32/f32 tensors), per-leaf rows
-// (device int32, concatenated) + offsets + leaf node ids.
+// (device int32, concatenated) + offsets + leaf node ids, and preds_applied.
+// rows_identity promises rows_root[i] == i for all i (every row, in order).
+// With preds_col the tree's update, preds_col[row] += (float)((double)leaf
+// value * shrinkage), is launched on the caller's stream before returning.
 py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
                           torch::Tensor rows_root,
                           torch::Tensor grad, torch::Tensor hess,
@@ -502,10 +548,31 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
                           c10::optional<torch::Tensor> feat_mask,
                           c10::optional<torch::Tensor> cat_feats,
                           double cat_smooth,
-                          py::object process_group, bool distributed) {
+                          py::object process_group, bool distributed,
+                          bool rows_identity,
+                          c10::optional<torch::Tensor> preds_col,
+                          double shrinkage) {
   GrowCtx ctx;
   const long n_full = binned_pair.size(1);
   ctx.n_arena = rows_root.numel();
+  // rows_identity: rows_root[i] == i for every i, so buffer 0's planes would
+  // be a copy of binned_pair and the root reads binned_pair instead
+  const bool root_static =
+      grower_switch("MMLSPARK_AMD_GROWER_ROOT_STATIC") && rows_identity;
+  const bool root_one_wait = grower_switch("MMLSPARK_AMD_GROWER_ROOT_ONE_WAIT");
+  const bool apply_here =
+      grower_switch("MMLSPARK_AMD_GROWER_APPLY") && preds_col.has_value();
+  if (rows_identity)
+    TORCH_CHECK(ctx.n_arena == n_full && binned_pair.is_contiguous() &&
+                binned_pair.scalar_type() == torch::kInt64,
+                "rows_identity needs rows_root to be all ", n_full,
+                " rows and contiguous i64 bin planes, got ", ctx.n_arena,
+                " rows");
+  if (preds_col.has_value())
+    TORCH_CHECK(preds_col->is_cuda() && preds_col->dim() == 1 &&
+                preds_col->scalar_type() == torch::kFloat32 &&
+                preds_col->size(0) >= n_full,
+                "preds_col: 1-D f32 device tensor over all rows");
   ctx.n_bins = (int)n_bins;
   ctx.npairs = (int)binned_pair.size(0);
   ctx.tail_bytes = (int)(binned.size(0) * 4 - (ctx.npairs - 1) * 8);
@@ -561,10 +628,14 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
                                 rows_root.options().dtype(torch::kInt32));
   }
   // materialize arena buffer 0: bin pairs + quantized (gq,hq) + row ids for
-  // the (possibly bagged) root row set
+  // the (possibly bagged) root row set; with the root on the static planes
+  // no plane is copied (zero planes) and pair[0] is first written by the
+  // root's grandchildren
+  if (root_static) ctx.root_pair = binned_pair.data_ptr();
   launch_arena_gather(binned_pair.data_ptr(), n_full,
                       grad.data_ptr<float>(), hess.data_ptr<float>(),
-                      rows_root.data_ptr<int>(), ctx.n_arena, ctx.npairs,
+                      rows_root.data_ptr<int>(), ctx.n_arena,
+                      root_static ? 0 : ctx.npairs,
                       ctx.scale_g, ctx.scale_h, ctx.pair[0].data_ptr(),
                       ctx.ghq[0].data_ptr(), ctx.rowid[0].data_ptr<int>(),
                       grower_stream());
@@ -579,19 +650,29 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
     return (int)feature_.size() - 1;
   };
 
-  auto root_hist = build_hist(ctx, 0, 0, ctx.n_arena);
-  auto sums = root_hist.select(0, 0).sum(0).to(torch::kCPU);
-  auto sa = sums.accessor<int64_t, 1>();
-  const double G0 = (double)sa[0] / scale_g;
-  const double H0 = (double)sa[1] / scale_h;
-  const double C0 = (double)sa[2];
-
+  const int root_buf = root_static ? kRootBuf : 0;
+  auto root_hist = build_hist(ctx, root_buf, 0, ctx.n_arena);
   auto root = std::make_shared<LeafCand>();
   root->node_id = new_node();
-  root->lo = 0; root->hi = ctx.n_arena; root->buf = 0;
+  root->lo = 0; root->hi = ctx.n_arena; root->buf = root_buf;
   root->hist = root_hist;
-  root->G = G0; root->H = H0; root->C = C0;
-  {
+  // root totals = feature 0's histogram row summed over its bins, in int64
+  int64_t s0[3] = {0, 0, 0};
+  if (root_one_wait) {
+    // the row rides back behind the same event as the root scan's records
+    // and is summed on the host: exact, so equal to a device reduction
+    SplitJob j;
+    launch_scan_async(ctx, torch::Tensor(), root_hist, torch::Tensor(), true,
+                      j, /*row0=*/true);
+    (void)hipEventSynchronize(j.ev);
+    const int64_t* r = j.row0_host.data_ptr<int64_t>();
+    for (int b = 0; b < ctx.n_bins; ++b)
+      for (int c = 0; c < 3; ++c) s0[c] += r[b * 3 + c];
+    resolve_best(ctx, j, 0, *root);
+  } else {
+    auto sums = root_hist.select(0, 0).sum(0).to(torch::kCPU);
+    auto sa = sums.accessor<int64_t, 1>();
+    for (int c = 0; c < 3; ++c) s0[c] = sa[c];
     // one-time root scan through the same async machinery
     SplitJob j;
     launch_scan_async(ctx, torch::Tensor(), root_hist, torch::Tensor(), true,
@@ -599,6 +680,10 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
     (void)hipEventSynchronize(j.ev);
     resolve_best(ctx, j, 0, *root);
   }
+  const double G0 = (double)s0[0] / scale_g;
+  const double H0 = (double)s0[1] / scale_h;
+  const double C0 = (double)s0[2];
+  root->G = G0; root->H = H0; root->C = C0;
   count_[root->node_id] = (float)C0;
   value_[root->node_id] = (float)leaf_output(G0, H0, l1, l2, max_delta);
 
@@ -667,7 +752,7 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
     auto rc = std::make_shared<LeafCand>();
     lc->node_id = lid; rc->node_id = rid;
     lc->depth = rc->depth = leaf->depth + 1;
-    lc->buf = rc->buf = leaf->buf ^ 1;
+    lc->buf = rc->buf = child_buf(leaf->buf);
     lc->lo = leaf->lo; lc->hi = leaf->lo + nl;
     rc->lo = leaf->lo + nl; rc->hi = leaf->lo + m_parent;
     lc->hist = job.hist_l; rc->hist = job.hist_r;
@@ -708,8 +793,8 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
   std::vector<int64_t> seg_nodes;
   for (size_t i = 0; i < finals.size(); ++i) {
     leaf_idx_[finals[i]->node_id] = (int)i;
-    segs.push_back(ctx.rowid[finals[i]->buf].slice(0, finals[i]->lo,
-                                                   finals[i]->hi));
+    segs.push_back(ctx.rowid[small_buf(finals[i]->buf)].slice(
+        0, finals[i]->lo, finals[i]->hi));
     seg_nodes.push_back(finals[i]->node_id);
   }
   auto leaf_rows = segs.empty()
@@ -717,6 +802,29 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
                        : torch::cat(segs);
   std::vector<int64_t> offs(1, 0);
   for (auto& s : segs) offs.push_back(offs.back() + s.numel());
+
+  // prediction update, launched here so that it runs while the caller builds
+  // its tree object: preds_col[row] += (float)(leaf value * shrinkage).  The
+  // offsets and values go up from pinned tensors without blocking; torch's
+  // host allocator keeps them alive until the copies are done.
+  const bool applied = apply_here && leaf_rows.numel() > 0;
+  if (applied) {
+    const long nl = (long)segs.size();
+    auto pin = torch::TensorOptions().pinned_memory(true);
+    auto offs_h = torch::empty({nl + 1}, pin.dtype(torch::kInt64));
+    auto vals_h = torch::empty({nl}, pin.dtype(torch::kFloat32));
+    std::copy(offs.begin(), offs.end(), offs_h.data_ptr<int64_t>());
+    for (long i = 0; i < nl; ++i)
+      vals_h.data_ptr<float>()[i] =
+          (float)((double)value_[seg_nodes[i]] * shrinkage);
+    auto offs_d = offs_h.to(leaf_rows.device(), /*non_blocking=*/true);
+    auto vals_d = vals_h.to(leaf_rows.device(), /*non_blocking=*/true);
+    launch_apply_leaf_values(preds_col->data_ptr<float>(),
+                             preds_col->stride(0), leaf_rows.data_ptr<int>(),
+                             (const long*)offs_d.data_ptr<int64_t>(), (int)nl,
+                             vals_d.data_ptr<float>(), leaf_rows.numel(),
+                             grower_stream());
+  }
 
   py::gil_scoped_acquire gil;
   auto i32 = torch::TensorOptions().dtype(torch::kInt32);
@@ -737,6 +845,8 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
   d["cat_words"] = cat_words_.empty()
                        ? torch::zeros({0}, i32)
                        : torch::tensor(cat_words_, i32);
+  // (1,) i32: 1 iff preds_col already holds this tree's update
+  d["preds_applied"] = torch::full({1}, applied ? 1 : 0, i32);
   return d;
 }
 
@@ -871,7 +981,15 @@ void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grow_tree_native", &grow_tree_native,
-        "native leaf-wise GBDT tree growth (numeric features, arena mode)");
+        "native leaf-wise GBDT tree growth (arena mode)", py::arg("binned"),
+        py::arg("binned_pair"), py::arg("rows_root"), py::arg("grad"),
+        py::arg("hess"), py::arg("n_bins"), py::arg("nf"), py::arg("scale_g"),
+        py::arg("scale_h"), py::arg("l1"), py::arg("l2"), py::arg("min_data"),
+        py::arg("min_hess"), py::arg("min_gain"), py::arg("max_delta"),
+        py::arg("num_leaves"), py::arg("max_depth"), py::arg("feat_mask"),
+        py::arg("cat_feats"), py::arg("cat_smooth"), py::arg("process_group"),
+        py::arg("distributed"), py::arg("rows_identity") = false,
+        py::arg("preds_col") = py::none(), py::arg("shrinkage") = 1.0);
   m.def("apply_leaf_values", &apply_leaf_values,
         "preds_col[leaf_rows] += per-leaf value, one kernel");
   m.def("partition_arena", &partition_arena,
