@@ -623,9 +623,33 @@ class LightGBMRanker(_GBDTEstimatorBase):
         eval_at = list(self.get("evalAt") or [self.get("maxPosition")])
         gains_tbl = self.get("labelGain")
         sizes = (valid_groups.tolist() if valid_groups is not None else None)
+        device_eval = {}  # labels tensor id -> (labels, NdcgEvaluator)
+
+        def on_device(raw, yv):
+            # ranks from group_rank_k, segment sums on the device, the ideal
+            # DCG per (group, k) built once per labelled set
+            from .ranking import NdcgEvaluator, offsets_from_sizes
+            hit = device_eval.get(id(yv))
+            if hit is None or hit[0] is not yv:
+                n = yv.numel()
+                offsets = offsets_from_sizes(sizes if sizes else [n], n)
+                hit = (yv, NdcgEvaluator(yv, offsets, eval_at, gains_tbl))
+                device_eval[id(yv)] = hit
+            return hit[1](raw)
 
         def fn(booster, Xv, yv, wv, comm):
             raw = booster.predict_raw(Xv).squeeze(-1)
+            from .ranking import kernel_path_enabled
+            # the groups given describe the validation split; any other set
+            # (training metrics) keeps the loop's handling of them
+            fits = not sizes or sum(int(sz) for sz in sizes) == yv.numel()
+            if raw.is_cuda and fits and kernel_path_enabled():
+                out = {}
+                for k, m in zip(eval_at, on_device(raw, yv)):
+                    t = torch.tensor([m, 1.0], device=Xv.device)
+                    comm.all_reduce(t)
+                    out[f"ndcg@{int(k)}"] = float(t[0] / t[1])
+                return out
             scores = raw.cpu().numpy()
             y = yv.cpu().numpy()
             group_sizes = sizes if sizes else [len(y)]

@@ -207,6 +207,10 @@ class LambdarankObjective(Objective):
 
     The ranker path of the reference (LightGBMRanker.scala:26; group column
     semantics params/LightGBMParams.scala:76). group_sizes set per-fit.
+
+    Device tensors go through two HIP kernels for all groups at once
+    (ops/hip/rank_kernels.hip) unless MMLSPARK_AMD_LAMBDARANK=0; CPU tensors
+    take the per-group loop.
     """
     name = "lambdarank"
     higher_better_metric = True
@@ -215,7 +219,32 @@ class LambdarankObjective(Objective):
         self.sigmoid = sigmoid
         self.label_gain = label_gain
         self.truncation = truncation
-        self.group_sizes: Optional[Tensor] = None
+        self._rank_inputs = None  # (label, label version, device, RankInputs)
+        self.group_sizes = None
+
+    @property
+    def group_sizes(self) -> Optional[Tensor]:
+        return self._group_sizes
+
+    @group_sizes.setter
+    def group_sizes(self, sizes: Optional[Tensor]):
+        # every session assigns its own groups (one per numBatches batch):
+        # the kernel inputs derived from them are rebuilt on next use
+        self._group_sizes = sizes
+        self._rank_inputs = None
+
+    def _device_inputs(self, label: Tensor, device):
+        """Per-fit inputs of the rank kernels, built (and validated) on
+        first use and kept until the groups or the label tensor change."""
+        c = self._rank_inputs
+        if (c is None or c[0] is not label or c[1] != label._version
+                or c[2] != device):
+            from .ranking import build_rank_inputs
+            c = (label, label._version, device,
+                 build_rank_inputs(self._group_sizes, label, self._gains,
+                                   self.label_gain, device))
+            self._rank_inputs = c
+        return c[3]
 
     def _gains(self, label: Tensor) -> Tensor:
         if self.label_gain is not None:
@@ -226,6 +255,10 @@ class LambdarankObjective(Objective):
 
     def grad_hess(self, preds, label, weight):
         assert self.group_sizes is not None, "ranker requires group sizes"
+        if preds.is_cuda:
+            from .ranking import kernel_path_enabled
+            if kernel_path_enabled():
+                return self._grad_hess_device(preds, label, weight)
         s = preds.squeeze(-1)
         g = torch.zeros_like(s)
         h = torch.zeros_like(s)
@@ -240,6 +273,22 @@ class LambdarankObjective(Objective):
             g[sl] = gi
             h[sl] = hi
             start += sz
+        g, h = g.unsqueeze(-1), h.unsqueeze(-1).clamp_min(1e-16)
+        return self._apply_weight(g, h, weight)
+
+    def _grad_hess_device(self, preds, label, weight):
+        """Every group in two launches (group_rank_k, lambdarank_grad_k):
+        no per-group loop, no host synchronisation.  Same pairs and formulas
+        as _group_grads; ties in score are ranked by index."""
+        from ...ops import backend
+        inp = self._device_inputs(label, preds.device)
+        s = preds.reshape(-1).to(torch.float32).contiguous()
+        if s.numel() != inp.n:
+            raise ValueError("preds must have one score per label")
+        _, rec = backend.group_rank(s, inp.offsets, inp.gid, inp.label,
+                                    inp.gain, inp.disc_tbl)
+        g, h = backend.lambdarank_grad(rec, inp.offsets, inp.gid,
+                                       inp.inv_idcg, self.sigmoid)
         g, h = g.unsqueeze(-1), h.unsqueeze(-1).clamp_min(1e-16)
         return self._apply_weight(g, h, weight)
 

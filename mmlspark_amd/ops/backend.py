@@ -267,6 +267,30 @@ def tree_shap_csr(node_feature, node_threshold, node_left, node_right,
         cat_words).to(torch.float32)
 
 
+# ------------------------------------------------------------------ ranking
+def group_rank(score, offsets, gid, label, gain, disc_tbl):
+    """Stable descending rank of each document inside its query group
+    ((n,) int32, equal to the inverse of np.argsort(-s, kind="stable") per
+    group) and the (n, 4) records [s, label, gain, disc_tbl[rank]] that
+    lambdarank_grad reads.  offsets (G+1) int64, gid (n) int32; the group
+    table is validated where it is built (models/gbdt/ranking.py)."""
+    if score.is_cuda:
+        return _require_ext().group_rank(score, offsets, gid, label, gain,
+                                         disc_tbl)
+    return cpu_ref.group_rank(score, offsets, gid, label, gain, disc_tbl)
+
+
+def lambdarank_grad(records, offsets, gid, inv_idcg, sigma):
+    """Lambdarank (g, h) per document from group_rank's records, every query
+    group in one launch; inv_idcg (G) is the reciprocal ideal DCG per group.
+    Unclamped and unweighted: the objective does both afterwards."""
+    if records.is_cuda:
+        return _require_ext().lambdarank_grad(records, offsets, gid, inv_idcg,
+                                              float(sigma))
+    return cpu_ref.lambdarank_grad(records, offsets, gid, inv_idcg,
+                                   float(sigma))
+
+
 # ------------------------------------------------------------------- images
 JPEG_MAX_PIXELS = 1 << 26
 

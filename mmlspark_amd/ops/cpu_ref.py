@@ -505,3 +505,75 @@ def jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off, out):
             img = torch.stack([_jpeg_u8(r), _jpeg_u8(g), _jpeg_u8(b)], dim=2)
         out[out_off:out_off + img.numel()] = img.reshape(-1)
     return out
+
+
+# ------------------------------------------------------------------ ranking
+def group_rank(score: torch.Tensor, offsets: torch.Tensor, gid: torch.Tensor,
+               label: torch.Tensor, gain: torch.Tensor,
+               disc_tbl: torch.Tensor):
+    """Stable descending rank of every document inside its query group, and
+    the per-document records lambdarank_grad reads — matches group_rank_k.
+
+    rank[i] counts the documents j of i's group with
+    s_j > s_i or (s_j == s_i and j < i), so it equals the inverse of
+    np.argsort(-s, kind="stable") per group and lies in [0, m) for any
+    scores.  Generic in dtype: the records take score's dtype.
+    returns (rank (n,) int32, records (n, 4) [s, label, gain, disc_tbl[rank]]).
+    """
+    n = score.numel()
+    dt = score.dtype
+    rank = torch.zeros(n, dtype=torch.int64)
+    offs = offsets.tolist()
+    for b, e in zip(offs[:-1], offs[1:]):
+        if e - b <= 1:
+            continue
+        s = score[b:e]
+        idx = torch.arange(e - b)
+        ahead = (s.unsqueeze(0) > s.unsqueeze(1)) | (
+            (s.unsqueeze(0) == s.unsqueeze(1))
+            & (idx.unsqueeze(0) < idx.unsqueeze(1)))
+        rank[b:e] = ahead.sum(dim=1)
+    rec = torch.stack([score, label.to(dt), gain.to(dt),
+                       disc_tbl.to(dt)[rank]], dim=1)
+    return rank.to(torch.int32), rec
+
+
+def lambdarank_grad(records: torch.Tensor, offsets: torch.Tensor,
+                    gid: torch.Tensor, inv_idcg: torch.Tensor, sigma: float):
+    """Lambdarank gradient and hessian per document — matches
+    lambdarank_grad_k, in the dtype of `records` (float32 is the kernel's
+    reference, float64 an evaluation of the same formulas).
+
+    Over every j of i's group with label_i != label_j, hi being the one with
+    the larger label and x = sigma * (s_hi - s_lo):
+      e = exp(-|x|), q = 1 / (1 + e), rho = q if x < 0 else e * q
+      delta = |gain_i - gain_j| * |disc_i - disc_j| * inv_idcg[group]
+      g_i -= sigma * rho * delta if i is hi else += ;
+      h_i += sigma^2 * (e * q * q) * delta
+    Groups of size 0 or 1 and documents without such a partner get exactly 0.
+    """
+    n = records.shape[0]
+    g = torch.zeros(n, dtype=records.dtype)
+    h = torch.zeros(n, dtype=records.dtype)
+    inv = inv_idcg.to(records.dtype)
+    offs = offsets.tolist()
+    for k, (b, e) in enumerate(zip(offs[:-1], offs[1:])):
+        if e - b <= 1:
+            continue
+        s, y, gn, d = records[b:e].unbind(dim=1)
+        differ = y.unsqueeze(1) != y.unsqueeze(0)
+        i_hi = y.unsqueeze(1) > y.unsqueeze(0)
+        ds = s.unsqueeze(1) - s.unsqueeze(0)
+        x = sigma * torch.where(i_hi, ds, -ds)
+        ex = torch.exp(-x.abs())
+        q = 1.0 / (1.0 + ex)
+        eq = ex * q
+        rho = torch.where(x < 0, q, eq)
+        delta = ((gn.unsqueeze(1) - gn.unsqueeze(0)).abs()
+                 * (d.unsqueeze(1) - d.unsqueeze(0)).abs() * inv[k])
+        t = sigma * rho * delta
+        zero = torch.zeros_like(t)
+        g[b:e] = torch.where(differ, torch.where(i_hi, -t, t), zero).sum(dim=1)
+        h[b:e] = torch.where(differ, (sigma * sigma) * (eq * q) * delta,
+                             zero).sum(dim=1)
+    return g, h

@@ -74,6 +74,12 @@ void launch_csr_partition(const long*, const int*, const unsigned char*,
 void launch_jpeg_reconstruct(const short*, const unsigned short*, const long*,
                              const long*, const long*, int, long,
                              unsigned char*, hipStream_t);
+void launch_group_rank(const float*, const long*, const int*, const float*,
+                       const float*, const float*, long, int, long, int*,
+                       void*, hipStream_t);
+void launch_lambdarank_grad(const void*, const long*, const int*,
+                            const float*, float, long, int, float*, float*,
+                            hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -574,6 +580,79 @@ void jpeg_reconstruct(torch::Tensor coef, torch::Tensor qt,
       n_items, out.data_ptr<uint8_t>(), cur_stream());
 }
 
+// ------------------------------------------------------------------ ranking
+// Shared checks of the per-fit group table (rank_kernels.hip): offsets
+// (G+1) int64, gid (n) int32.  Their contents are validated on the host when
+// they are built (models/gbdt/ranking.py); the kernels clamp what is left.
+static void check_group_table(const torch::Tensor& offsets,
+                              const torch::Tensor& gid, long n) {
+  CHECK_DEV(offsets); CHECK_CONTIG(offsets);
+  CHECK_DEV(gid); CHECK_CONTIG(gid);
+  TORCH_CHECK(offsets.dtype() == torch::kInt64, "offsets must be int64");
+  TORCH_CHECK(gid.dtype() == torch::kInt32, "gid must be int32");
+  TORCH_CHECK(offsets.dim() == 1 && offsets.numel() >= 1,
+              "offsets must be a (G+1) vector");
+  TORCH_CHECK(offsets.numel() - 1 < (1L << 31), "too many groups");
+  TORCH_CHECK(gid.dim() == 1 && gid.numel() == n,
+              "gid must have one entry per document");
+  TORCH_CHECK(n < (1L << 31), "too many documents for int32 ranks");
+}
+
+std::tuple<torch::Tensor, torch::Tensor> group_rank(
+    torch::Tensor score, torch::Tensor offsets, torch::Tensor gid,
+    torch::Tensor label, torch::Tensor gain, torch::Tensor disc_tbl) {
+  CHECK_DEV(score); CHECK_CONTIG(score);
+  CHECK_DEV(label); CHECK_CONTIG(label);
+  CHECK_DEV(gain); CHECK_CONTIG(gain);
+  CHECK_DEV(disc_tbl); CHECK_CONTIG(disc_tbl);
+  TORCH_CHECK(score.dtype() == torch::kFloat32 &&
+              label.dtype() == torch::kFloat32 &&
+              gain.dtype() == torch::kFloat32 &&
+              disc_tbl.dtype() == torch::kFloat32,
+              "score, label, gain and disc_tbl must be float32");
+  TORCH_CHECK(score.dim() == 1, "score must be a vector");
+  const long n = score.numel();
+  check_group_table(offsets, gid, n);
+  TORCH_CHECK(label.numel() == n && gain.numel() == n,
+              "label and gain must have one entry per document");
+  auto rank = torch::empty({n}, score.options().dtype(torch::kInt32));
+  auto rec = torch::empty({n, 4}, score.options());
+  if (n == 0) return {rank, rec};
+  launch_group_rank(score.data_ptr<float>(), offsets.data_ptr<long>(),
+                    gid.data_ptr<int>(), label.data_ptr<float>(),
+                    gain.data_ptr<float>(), disc_tbl.data_ptr<float>(), n,
+                    (int)(offsets.numel() - 1), disc_tbl.numel(),
+                    rank.data_ptr<int>(), rec.data_ptr(), cur_stream());
+  return {rank, rec};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> lambdarank_grad(
+    torch::Tensor records, torch::Tensor offsets, torch::Tensor gid,
+    torch::Tensor inv_idcg, double sigma) {
+  CHECK_DEV(records); CHECK_CONTIG(records);
+  CHECK_DEV(inv_idcg); CHECK_CONTIG(inv_idcg);
+  TORCH_CHECK(records.dtype() == torch::kFloat32 &&
+              inv_idcg.dtype() == torch::kFloat32,
+              "records and inv_idcg must be float32");
+  TORCH_CHECK(records.dim() == 2 && records.size(1) == 4,
+              "records must be (n, 4)");
+  const long n = records.size(0);
+  check_group_table(offsets, gid, n);
+  TORCH_CHECK(inv_idcg.numel() == offsets.numel() - 1,
+              "inv_idcg must have one entry per group");
+  auto g = torch::empty({n}, records.options());
+  auto h = torch::empty({n}, records.options());
+  if (n == 0) return {g, h};
+  TORCH_CHECK(((uintptr_t)records.data_ptr() & 15) == 0,
+              "records must be 16-byte aligned");
+  launch_lambdarank_grad(records.data_ptr(), offsets.data_ptr<long>(),
+                         gid.data_ptr<int>(), inv_idcg.data_ptr<float>(),
+                         (float)sigma, n, (int)(offsets.numel() - 1),
+                         g.data_ptr<float>(), h.data_ptr<float>(),
+                         cur_stream());
+  return {g, h};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -605,4 +684,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wave-cooperative CSR histogram + in-kernel leaf totals");
   m.def("jpeg_reconstruct", &jpeg_reconstruct,
         "batched JPEG dequant + IDCT + colour conversion into a uint8 buffer");
+  m.def("group_rank", &group_rank,
+        "stable descending in-group ranks + per-document rank records");
+  m.def("lambdarank_grad", &lambdarank_grad,
+        "lambdarank gradients and hessians over all query groups");
 }
