@@ -291,6 +291,77 @@ def lambdarank_grad(records, offsets, gid, inv_idcg, sigma):
                                    float(sigma))
 
 
+# ------------------------------------------------------- nearest neighbours
+KNN_MAX_K = 64        # knn_partial_topk_k keeps k <= 64 pairs per query in LDS
+KNN_MAX_SPLITS = 64   # knn_merge_k holds splits * k pairs in LDS
+
+
+def check_knn_inputs(Q, X, xsq, k, label_ids, allow_bits, splits):
+    """Everything the knn kernels index with, checked in O(inputs); raises
+    ValueError and nothing is launched."""
+    def bad(msg):
+        raise ValueError("knn_topk: " + msg)
+
+    for name, t in (("Q", Q), ("X", X), ("xsq", xsq)):
+        if t.dtype != torch.float32:
+            bad(name + " must be float32")
+        if not t.is_contiguous():
+            bad(name + " must be contiguous")
+        if t.device != X.device:
+            bad(name + " must live where X lives")
+    if Q.dim() != 2 or X.dim() != 2 or X.shape[1] < 1 \
+            or Q.shape[1] != X.shape[1]:
+        bad("Q (n_q, d) and X (n, d) must agree on d >= 1")
+    n_q, n = Q.shape[0], X.shape[0]
+    if n >= (1 << 31):
+        bad("n_index must be below 2^31")
+    if xsq.dim() != 1 or xsq.shape[0] != n:
+        bad("xsq must hold one squared norm per index row")
+    if not 1 <= int(k) <= KNN_MAX_K:
+        bad("k must be in [1, %d]" % KNN_MAX_K)
+    if not 0 <= int(splits) <= KNN_MAX_SPLITS:
+        bad("splits must be in [0, %d] (0 = automatic)" % KNN_MAX_SPLITS)
+    if (label_ids is None) != (allow_bits is None):
+        bad("label_ids and allow_bits must be given together")
+    if label_ids is None:
+        return
+    for name, t in (("label_ids", label_ids), ("allow_bits", allow_bits)):
+        if t.dtype != torch.int32:
+            bad(name + " must be int32")
+        if not t.is_contiguous():
+            bad(name + " must be contiguous")
+        if t.device != X.device:
+            bad(name + " must live where X lives")
+    if label_ids.dim() != 1 or label_ids.shape[0] != n:
+        bad("label_ids must hold one label id per index row")
+    if allow_bits.dim() != 2 or allow_bits.shape[0] != n_q \
+            or allow_bits.shape[1] < 1:
+        bad("allow_bits must be (n_q, W) with W >= 1")
+    if n and (int(label_ids.min()) < 0
+              or int(label_ids.max()) >= 32 * allow_bits.shape[1]):
+        bad("label_ids must lie in [0, 32 * W)")
+
+
+def knn_topk(Q, X, xsq, k, label_ids=None, allow_bits=None, splits=0):
+    """Exact k nearest index rows of every query, 1 <= k <= KNN_MAX_K, under
+    the total order (squared distance ascending, index ascending).
+
+    Q (n_q, d), X (n, d), xsq (n) = row sums of X*X, all float32.  With
+    label_ids (n) int32 and allow_bits (n_q, W) int32, point j is a candidate
+    for query i only if bit label_ids[j] of row i is set (word label >> 5,
+    bit label & 31, words read as unsigned).  splits > 0 fixes how many
+    pieces the index is cut into on the device; the result does not depend
+    on it.  Returns (d2 (n_q, k) float32 = ||q||^2 - 2 q.x + ||x||^2,
+    unclamped, idx (n_q, k) int32); a query with fewer than k candidates has
+    (+inf, -1) in its last slots."""
+    check_knn_inputs(Q, X, xsq, k, label_ids, allow_bits, splits)
+    if X.is_cuda:
+        return _require_ext().knn_topk(Q, X, xsq, int(k), label_ids,
+                                       allow_bits, int(splits))
+    return cpu_ref.knn_topk(Q, X, xsq, int(k), label_ids, allow_bits,
+                            int(splits))
+
+
 # ------------------------------------------------------------------- images
 JPEG_MAX_PIXELS = 1 << 26
 

@@ -577,3 +577,71 @@ def lambdarank_grad(records: torch.Tensor, offsets: torch.Tensor,
         h[b:e] = torch.where(differ, (sigma * sigma) * (eq * q) * delta,
                              zero).sum(dim=1)
     return g, h
+
+
+# ------------------------------------------------------- nearest neighbours
+def _knn_allowed(label_ids, allow_bits, lo, hi):
+    """(hi - lo, n) bool: bit label_ids[j] of query i's bitset, the words
+    read as unsigned."""
+    lid = label_ids.long()
+    words = allow_bits[lo:hi].long()[:, lid >> 5] & 0xFFFFFFFF
+    return ((words >> (lid & 31).unsqueeze(0)) & 1).bool()
+
+
+def _knn_select(d2, k):
+    """First k of every row under (d2 ascending, index ascending); slots
+    whose distance is +inf become (+inf, -1)."""
+    srt, order = torch.sort(d2, dim=1, stable=True)
+    srt, order = srt[:, :k], order[:, :k]
+    pad = k - srt.shape[1]
+    if pad > 0:
+        srt = torch.nn.functional.pad(srt, (0, pad), value=float("inf"))
+        order = torch.nn.functional.pad(order, (0, pad), value=-1)
+    order = torch.where(torch.isinf(srt) & (srt > 0),
+                        torch.full_like(order, -1), order)
+    return srt, order.to(torch.int32)
+
+
+def _knn_run(Q, X, k, label_ids, allow_bits, dist_fn, dtype, row_cost):
+    n_q = Q.shape[0]
+    out_d = torch.full((n_q, k), float("inf"), dtype=dtype)
+    out_i = torch.full((n_q, k), -1, dtype=torch.int32)
+    if X.shape[0] == 0:
+        return out_d, out_i
+    step = max(1, (1 << 24) // max(1, row_cost))
+    for lo in range(0, n_q, step):
+        hi = min(n_q, lo + step)
+        d2 = dist_fn(Q[lo:hi])
+        if label_ids is not None:
+            d2 = torch.where(_knn_allowed(label_ids, allow_bits, lo, hi), d2,
+                             torch.full_like(d2, float("inf")))
+        out_d[lo:hi], out_i[lo:hi] = _knn_select(d2, k)
+    return out_d, out_i
+
+
+def knn_topk(Q, X, xsq, k, label_ids=None, allow_bits=None, splits=0):
+    """The k nearest index rows of every query under the total order
+    (d2 ascending, index ascending) — the contract of knn_partial_topk_k +
+    knn_merge_k, in float32 with torch's GEMM: d2 = (xsq - 2 q.x) + ||q||^2,
+    unclamped.  A point whose label bit is not set in the query's bitset
+    (allow_bits (n_q, W) int32, read as unsigned) is left out; a query with
+    fewer than k allowed points gets (+inf, -1) in the remaining slots.
+    `splits` only shapes the device launch.  Returns (d2 (n_q, k) float32,
+    idx (n_q, k) int32)."""
+    def dist(q):
+        return (xsq.unsqueeze(0) - 2.0 * (q @ X.t())) \
+            + (q * q).sum(1, keepdim=True)
+    return _knn_run(Q, X, k, label_ids, allow_bits, dist, torch.float32,
+                    X.shape[0])
+
+
+def knn_topk_f64(Q, X, k, label_ids=None, allow_bits=None):
+    """knn_topk's answer from float64 distances sum((q - x)^2): the exact
+    order on integer data.  Returns (D (n_q, k) float64, idx int32)."""
+    Xd = X.double()
+
+    def dist(q):
+        diff = q.double().unsqueeze(1) - Xd.unsqueeze(0)
+        return (diff * diff).sum(2)
+    return _knn_run(Q, Xd, k, label_ids, allow_bits, dist, torch.float64,
+                    X.shape[0] * X.shape[1])

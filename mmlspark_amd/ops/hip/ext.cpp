@@ -80,6 +80,10 @@ void launch_group_rank(const float*, const long*, const int*, const float*,
 void launch_lambdarank_grad(const void*, const long*, const int*,
                             const float*, float, long, int, float*, float*,
                             hipStream_t);
+int knn_choose_splits(long, long, int, int);
+int launch_knn_topk(const float*, const float*, const float*, const float*,
+                    const int*, const unsigned*, long, long, int, int, int,
+                    int, float*, int*, float*, int*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -653,6 +657,70 @@ std::tuple<torch::Tensor, torch::Tensor> lambdarank_grad(
   return {g, h};
 }
 
+// ------------------------------------------------------ nearest neighbours
+// knn_kernels.hip.  The contents of label_ids are range-checked by the caller
+// (ops/backend.py) and clamped again in the kernel.
+static const int kKnnMaxK = 64;
+static const int kKnnMaxSplits = 64;
+
+std::tuple<torch::Tensor, torch::Tensor> knn_topk(
+    torch::Tensor Q, torch::Tensor X, torch::Tensor xsq, long k,
+    c10::optional<torch::Tensor> label_ids,
+    c10::optional<torch::Tensor> allow_bits, long splits) {
+  CHECK_DEV(Q); CHECK_CONTIG(Q);
+  CHECK_DEV(X); CHECK_CONTIG(X);
+  CHECK_DEV(xsq); CHECK_CONTIG(xsq);
+  TORCH_CHECK(Q.dtype() == torch::kFloat32 && X.dtype() == torch::kFloat32 &&
+              xsq.dtype() == torch::kFloat32,
+              "Q, X and xsq must be float32");
+  TORCH_CHECK(Q.dim() == 2 && X.dim() == 2 && Q.size(1) == X.size(1),
+              "Q (n_q, d) and X (n, d) must agree on d");
+  const long n_q = Q.size(0), n = X.size(0), d = X.size(1);
+  TORCH_CHECK(xsq.dim() == 1 && xsq.numel() == n, "xsq must be (n,)");
+  TORCH_CHECK(k >= 1 && k <= kKnnMaxK, "k out of range");
+  TORCH_CHECK(n < (1L << 31) && d >= 1 && d < (1L << 24),
+              "index too large");
+  TORCH_CHECK(splits >= 0 && splits <= kKnnMaxSplits, "splits out of range");
+  TORCH_CHECK(label_ids.has_value() == allow_bits.has_value(),
+              "label_ids and allow_bits go together");
+  const int* lid = nullptr;
+  const unsigned* bits = nullptr;
+  int W = 0;
+  if (label_ids.has_value()) {
+    const auto& l = *label_ids;
+    const auto& b = *allow_bits;
+    CHECK_DEV(l); CHECK_CONTIG(l);
+    CHECK_DEV(b); CHECK_CONTIG(b);
+    TORCH_CHECK(l.dtype() == torch::kInt32 && l.dim() == 1 && l.numel() == n,
+                "label_ids must be (n,) int32");
+    TORCH_CHECK(b.dtype() == torch::kInt32 && b.dim() == 2 &&
+                b.size(0) == n_q && b.size(1) >= 1 && b.size(1) < (1L << 20),
+                "allow_bits must be (n_q, W) int32");
+    lid = l.data_ptr<int>();
+    bits = (const unsigned*)b.data_ptr<int>();
+    W = (int)b.size(1);
+  }
+  auto d2 = torch::full({n_q, k}, std::numeric_limits<float>::infinity(),
+                        Q.options());
+  auto idx = torch::full({n_q, k}, -1, Q.options().dtype(torch::kInt32));
+  if (n_q == 0 || n == 0) return {d2, idx};
+  const int sp = knn_choose_splits(n_q, n, (int)k, (int)splits);
+  const long q_tiles = (n_q + 127) / 128;
+  TORCH_CHECK(n_q < (1L << 31) && q_tiles * sp < (1L << 31),
+              "too many queries for one launch");
+  auto qsq = (Q * Q).sum(1);
+  auto part_s = torch::empty({n_q, sp, k}, Q.options());
+  auto part_i = torch::empty({n_q, sp, k}, idx.options());
+  const int err = launch_knn_topk(
+      Q.data_ptr<float>(), X.data_ptr<float>(), xsq.data_ptr<float>(),
+      qsq.data_ptr<float>(), lid, bits, n_q, n, (int)d, (int)k, W, sp,
+      part_s.data_ptr<float>(), part_i.data_ptr<int>(), d2.data_ptr<float>(),
+      idx.data_ptr<int>(), cur_stream());
+  TORCH_CHECK(err == 0, "knn_topk launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return {d2, idx};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -688,4 +756,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "stable descending in-group ranks + per-document rank records");
   m.def("lambdarank_grad", &lambdarank_grad,
         "lambdarank gradients and hessians over all query groups");
+  m.def("knn_topk", &knn_topk,
+        "fused exact k-nearest-neighbour search with optional label bitsets");
+  m.attr("KNN_MAX_K") = kKnnMaxK;
+  m.attr("KNN_MAX_SPLITS") = kKnnMaxSplits;
 }

@@ -19,7 +19,8 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 
 KERNEL_SOURCES = ["gbdt_kernels.hip", "vw_kernels.hip",
-                  "image_kernels.hip", "rank_kernels.hip"]
+                  "image_kernels.hip", "rank_kernels.hip",
+                  "knn_kernels.hip"]
 
 
 def compile_hip_kernels():
