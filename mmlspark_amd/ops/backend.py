@@ -125,6 +125,25 @@ def split_scan(hists, n_bins, l1, l2, min_data, min_hess, min_gain, nf_real,
                               min_gain, nf_real, feat_mask)
 
 
+def sibling_scan(parent, small, small_is_left, n_bins, l1, l2, min_data,
+                 min_hess, nf_real, feat_mask=None, scale_g=1.0, scale_h=1.0):
+    """The native grower's split scan (sibling_scan_k) on fixed-point int64
+    histograms (nf_pad, n_bins, 3) = [g*scale_g, h*scale_h, count].  With
+    `parent`, the other child's histogram big = parent - small is formed
+    and scanned in the same launch: returns (records (2, nf_pad, 6), big),
+    record row 0 the left child's and row 1 the right child's.  Without it
+    `small` is scanned alone: (records (1, nf_pad, 6), None).  A record is
+    one feature's {gain, feature, bin, GL, HL, CL}; the arg-max over
+    features (lowest feature on ties) is the caller's.  GPU-only."""
+    if not small.is_cuda:
+        raise RuntimeError("sibling_scan runs on the GPU only")
+    _require_ext()
+    from . import _hip_grower
+    return _hip_grower.sibling_scan(parent, small, bool(small_is_left),
+                                    int(n_bins), l1, l2, min_data, min_hess,
+                                    int(nf_real), feat_mask, scale_g, scale_h)
+
+
 def bin_matrix(X, upper_bounds, n_bins):
     if X.is_cuda:
         return _require_ext().bin_matrix(X, upper_bounds, n_bins)

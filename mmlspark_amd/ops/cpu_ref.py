@@ -338,7 +338,9 @@ def bin_matrix(X: torch.Tensor, upper_bounds: torch.Tensor,
     """
     n, nf = X.shape
     ng = (nf + 3) // 4
-    Xc = torch.nan_to_num(X, nan=-float("inf"))
+    # NaN -> -inf lands in bin 0; torch.where, because nan_to_num would also
+    # turn +-inf into +-FLT_MAX and move them across an infinite bound
+    Xc = torch.where(torch.isnan(X), torch.full_like(X, -float("inf")), X)
     bins = torch.searchsorted(upper_bounds.contiguous(),
                               Xc.t().contiguous(), right=False)
     bins = bins.clamp(max=n_bins - 1).to(torch.uint8)  # (nf, n)
@@ -374,6 +376,10 @@ def split_scan(hists: torch.Tensor, n_bins: int, l1: float, l2: float,
     neg = torch.full_like(gain, float("-inf"))
     gain = torch.where(valid, gain, neg)
     gain[..., -1] = float("-inf")
+    # a feature with at most one occupied bin never splits, whatever
+    # min_data says (the kernel's nz_bins <= 1 shortcut; LightGBM's rule)
+    degenerate = (c > 0).sum(dim=-1) <= 1
+    gain = torch.where(degenerate.unsqueeze(-1), neg, gain)
     if feat_mask is not None:
         gain[:, ~feat_mask, :] = float("-inf")
     gain[:, nf_real:, :] = float("-inf")

@@ -39,8 +39,7 @@ void launch_hist_build_fixed_pair(const void*, long, const int*, long,
 void launch_partition(const void*, long, const int*, long, int, int, int*,
                       int*, int*, hipStream_t);
 void launch_split_scan(const float*, int, long, int, float, float, float,
-                       float, float, long, const bool*, float*, float*,
-                       hipStream_t);
+                       float, long, const bool*, float*, float*, hipStream_t);
 void launch_vw_sgd(const int*, const float*, const long*, const float*,
                    const float*, float*, float*, float*, float, float, float,
                    int, int, long, float*, hipStream_t);
@@ -301,8 +300,16 @@ std::tuple<torch::Tensor, torch::Tensor> partition_rows(
 torch::Tensor bin_matrix(torch::Tensor X, torch::Tensor ub, long n_bins) {
   CHECK_DEV(X); CHECK_CONTIG(X);
   CHECK_DEV(ub); CHECK_CONTIG(ub);
+  // the bin is a uint8 and the kernel searches n_bins - 1 bounds per feature
+  TORCH_CHECK(n_bins >= 2 && n_bins <= 256, "n_bins must be in 2..256");
+  TORCH_CHECK(X.dim() == 2 && X.dtype() == torch::kFloat32,
+              "X must be (n, nf) float32");
+  TORCH_CHECK(X.device() == ub.device(), "ub must live where X lives");
   const long n = X.size(0);
   const long nf = X.size(1);
+  TORCH_CHECK(ub.dim() == 2 && ub.dtype() == torch::kFloat32 &&
+              ub.size(0) == nf && ub.size(1) == n_bins - 1,
+              "ub must be (nf, n_bins - 1) float32");
   const long ngroups = (nf + 3) / 4;
   auto out = torch::zeros({ngroups, n, 4}, X.options().dtype(torch::kUInt8));
   launch_bin_matrix(X.data_ptr<float>(), ub.data_ptr<float>(), n, (int)nf,
@@ -315,20 +322,35 @@ torch::Tensor split_scan(torch::Tensor hists, long n_bins, double l1,
                          double min_gain, long nf_real,
                          c10::optional<torch::Tensor> feat_mask) {
   // hists: (n_hists, nf_pad, n_bins, 3) — returns (n_hists, 6) on device:
-  // {gain, feature, bin, GL, HL, CL}
+  // {gain, feature, bin, GL, HL, CL}.  min_gain is not applied here: the
+  // record carries the gain and the threshold is the caller's.
+  (void)min_gain;
   CHECK_DEV(hists); CHECK_CONTIG(hists);
+  TORCH_CHECK(hists.dim() == 4 && hists.dtype() == torch::kFloat32 &&
+              hists.size(3) == 3,
+              "hists must be (n_hists, nf_pad, n_bins, 3) float32");
+  // one 256-thread block scans a feature: a bin per thread, 256 LDS slots
+  TORCH_CHECK(n_bins >= 2 && n_bins <= 256, "n_bins must be in 2..256");
+  TORCH_CHECK(hists.size(2) == n_bins, "n_bins must equal hists.size(2)");
   const long n_hists = hists.size(0);
   const long nf_pad = hists.size(1);
+  TORCH_CHECK(nf_real > 0 && nf_real <= nf_pad,
+              "nf_real must be in 1..nf_pad");
   auto scratch = torch::empty({n_hists, nf_pad, 6}, hists.options());
   auto out = torch::empty({n_hists, 6}, hists.options());
   const bool* mask_ptr = nullptr;
   if (feat_mask.has_value()) {
+    TORCH_CHECK(feat_mask->device() == hists.device(),
+                "feat_mask must live where hists lives");
     TORCH_CHECK(feat_mask->dtype() == torch::kBool, "feat_mask must be bool");
+    TORCH_CHECK(feat_mask->is_contiguous() && feat_mask->numel() >= nf_pad,
+                "feat_mask must be contiguous with at least nf_pad elements");
     mask_ptr = feat_mask->data_ptr<bool>();
   }
+  if (n_hists == 0) return out;
   launch_split_scan(hists.data_ptr<float>(), (int)n_hists, nf_pad,
                     (int)n_bins, (float)l1, (float)l2, (float)min_data,
-                    (float)min_hess, (float)min_gain, nf_real, mask_ptr,
+                    (float)min_hess, nf_real, mask_ptr,
                     scratch.data_ptr<float>(), out.data_ptr<float>(),
                     cur_stream());
   return out;

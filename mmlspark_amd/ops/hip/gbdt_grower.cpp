@@ -979,6 +979,65 @@ void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
                          threads_r, order_r, layout_r, grower_stream());
 }
 
+// Test entry for the fused sibling subtract + scan (sibling_scan_k), the
+// kernel launch_scan_async issues: `small` (nf_pad, n_bins, 3) int64 is one
+// child's fixed-point histogram as built; with `parent` the other child's is
+// formed as parent - small, stored into a fresh `big` and scanned in the same
+// launch (record row 0 = left child, row 1 = right child); without it `small`
+// is scanned alone (the root) and big is None.  Returns the per-feature
+// records (nh, nf_pad, 6) = {gain, feature, bin, GL, HL, CL}; the arg-max over
+// features is the caller's.  scale_g / scale_h are the fixed-point scales of
+// the g and h cells.  Everything the kernel indexes with is checked here.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> sibling_scan(
+    c10::optional<torch::Tensor> parent, torch::Tensor small,
+    bool small_is_left, long n_bins, double l1, double l2, double min_data,
+    double min_hess, long nf_real, c10::optional<torch::Tensor> feat_mask,
+    double scale_g, double scale_h) {
+  TORCH_CHECK(small.is_cuda() && small.is_contiguous() && small.dim() == 3 &&
+              small.scalar_type() == torch::kInt64 && small.size(2) == 3,
+              "small: contiguous (nf_pad, n_bins, 3) i64 device");
+  // one 256-thread block scans a feature: a bin per thread, 256 LDS slots
+  TORCH_CHECK(n_bins >= 2 && n_bins <= 256, "n_bins must be in 2..256");
+  TORCH_CHECK(small.size(1) == n_bins, "n_bins must equal small.size(1)");
+  const long nf_pad = small.size(0);
+  TORCH_CHECK(nf_real > 0 && nf_real <= nf_pad,
+              "nf_real must be in 1..nf_pad");
+  TORCH_CHECK(scale_g > 0 && scale_h > 0, "scales must be positive");
+  const long long* parent_ptr = nullptr;
+  if (parent.has_value()) {
+    TORCH_CHECK(parent->device() == small.device() &&
+                parent->is_contiguous() &&
+                parent->scalar_type() == torch::kInt64 &&
+                parent->sizes() == small.sizes(),
+                "parent: contiguous i64 of small's shape and device");
+    parent_ptr = (const long long*)parent->data_ptr<int64_t>();
+  }
+  const bool* mask = nullptr;
+  if (feat_mask.has_value()) {
+    TORCH_CHECK(feat_mask->device() == small.device(),
+                "feat_mask must live where small lives");
+    TORCH_CHECK(feat_mask->scalar_type() == torch::kBool,
+                "feat_mask must be bool");
+    TORCH_CHECK(feat_mask->is_contiguous() && feat_mask->numel() >= nf_pad,
+                "feat_mask must be contiguous with at least nf_pad elements");
+    mask = feat_mask->data_ptr<bool>();
+  }
+  const long nh = parent_ptr ? 2 : 1;
+  auto records = torch::empty(
+      {nh, nf_pad, 6},
+      torch::TensorOptions().dtype(torch::kFloat32).device(small.device()));
+  c10::optional<torch::Tensor> big;
+  if (parent_ptr) big = torch::empty_like(small);
+  launch_sibling_scan(
+      parent_ptr, (const long long*)small.data_ptr<int64_t>(),
+      big.has_value() ? (long long*)big->data_ptr<int64_t>() : nullptr,
+      small_is_left ? 1 : 0, nf_pad, (int)n_bins, (float)l1, (float)l2,
+      (float)min_data, (float)min_hess, nf_real, mask,
+      records.data_ptr<float>(), 1.0 / scale_g, 1.0 / scale_h,
+      grower_stream());
+  return {records, big};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grow_tree_native", &grow_tree_native,
         "native leaf-wise GBDT tree growth (arena mode)", py::arg("binned"),
@@ -1005,6 +1064,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nl_dev") = py::none(), py::arg("side") = -1,
         py::arg("chunk") = 0, py::arg("threads") = 0, py::arg("order") = -1,
         py::arg("layout") = -1);
+  m.def("sibling_scan", &sibling_scan,
+        "fused sibling subtract + per-feature split scan (records, big)",
+        py::arg("parent"), py::arg("small"), py::arg("small_is_left"),
+        py::arg("n_bins"), py::arg("l1"), py::arg("l2"), py::arg("min_data"),
+        py::arg("min_hess"), py::arg("nf_real"),
+        py::arg("feat_mask") = py::none(), py::arg("scale_g") = 1.0,
+        py::arg("scale_h") = 1.0);
   m.def("allreduce_native", &allreduce_native,
         "GIL-free c10d all_reduce through the same C++ path as the grower");
 }

@@ -1504,6 +1504,9 @@ extern "C" void launch_bin_matrix(const float* X, const float* ub, long n,
 // sibling_scan_k is the native grower's form: it reads int64 fixed-point
 // histograms directly (scales applied in-kernel), forms the sibling by
 // subtraction and leaves the reduce over features to the host.
+// Neither applies min_gain_to_split: a record carries its gain and the
+// threshold is the caller's.  The rules both follow (validity, ties, one
+// occupied bin) are written down in docs/kernels.md.
 
 // One feature's best split from its per-bin (g, h, count) already staged in
 // LDS as floats (slots >= n_bins zeroed); the caller syncs after staging.
@@ -1517,7 +1520,8 @@ DEV_INLINE void split_scan_feature(float* sg, float* sh, float* sc, int tid,
   // from this leaf — all mass in its zero bin) can never split validly;
   // skip the 3 prefix scans + gain pass.  Dominant on wide-sparse shapes
   // where most of 100k features are untouched per leaf.
-  const int nz_bins = __syncthreads_count(in && sc[tid] > 0.0f);
+  const bool occupied = in && sc[tid] > 0.0f;
+  const int nz_bins = __syncthreads_count(occupied);
   if (nz_bins <= 1) {
     if (tid == 0) {
       out[0] = -INFINITY; out[1] = (float)f; out[2] = 0;
@@ -1544,7 +1548,12 @@ DEV_INLINE void split_scan_feature(float* sg, float* sh, float* sc, int tid,
   const float parent = leaf_sc(G, Ht);
   float gain = -INFINITY;
   float GL = 0, HL = 0, CL = 0;
-  if (in && tid < n_bins - 1) {
+  // A split after an empty bin (tid > 0) selects the rows the split after
+  // the bin before it selects: in exact arithmetic the two tie and the first
+  // index wins, but the tree-shaped scan above rounds their prefix sums
+  // differently, so the later bin could win on rounding noise.  Only the
+  // first bin of such a tied run, the occupied one, is a candidate.
+  if (in && tid < n_bins - 1 && (tid == 0 || occupied)) {
     const float gl = sg[tid], hl = sh[tid], cl = sc[tid];
     const float gr = G - gl, hr = Ht - hl, cr = C - cl;
     if (cl >= min_data && cr >= min_data && hl >= min_hess && hr >= min_hess) {
@@ -1582,7 +1591,7 @@ DEV_INLINE void split_scan_feature(float* sg, float* sh, float* sc, int tid,
 
 __global__ void split_scan_k(const float* __restrict__ hist, int n_bins,
                              long nf_pad, float l1, float l2, float min_data,
-                             float min_hess, float min_gain, long nf_real,
+                             float min_hess, long nf_real,
                              const bool* __restrict__ feat_mask,
                              float* __restrict__ scratch) {
   const int f = blockIdx.x;
@@ -1740,13 +1749,13 @@ __global__ void split_reduce_k(const float* __restrict__ scratch, long nf_pad,
 extern "C" void launch_split_scan(const float* hist, int n_hists, long nf_pad,
                                   int n_bins, float l1, float l2,
                                   float min_data, float min_hess,
-                                  float min_gain, long nf_real,
-                                  const bool* feat_mask, float* scratch,
-                                  float* out, hipStream_t stream) {
+                                  long nf_real, const bool* feat_mask,
+                                  float* scratch, float* out,
+                                  hipStream_t stream) {
   dim3 grid1((unsigned)nf_pad, (unsigned)n_hists);
   hipLaunchKernelGGL(split_scan_k, grid1, dim3(256), 0, stream, hist, n_bins,
-                     nf_pad, l1, l2, min_data, min_hess, min_gain, nf_real,
-                     feat_mask, scratch);
+                     nf_pad, l1, l2, min_data, min_hess, nf_real, feat_mask,
+                     scratch);
   hipLaunchKernelGGL(split_reduce_k, dim3((unsigned)n_hists), dim3(256), 0,
                      stream, scratch, nf_pad, out);
 }
