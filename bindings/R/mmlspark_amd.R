@@ -1456,7 +1456,7 @@ ml_resize_image_transformer <- function(inputCol = NULL, outputCol = NULL, heigh
   stage
 }
 
-ml_sar <- function(userCol = NULL, itemCol = NULL, ratingCol = NULL, timeCol = NULL, supportThreshold = NULL, similarityFunction = NULL, timeDecayCoeff = NULL, startTime = NULL, startTimeFormat = NULL, activityTimeFormat = NULL) {
+ml_sar <- function(userCol = NULL, itemCol = NULL, ratingCol = NULL, timeCol = NULL, supportThreshold = NULL, similarityFunction = NULL, timeDecayCoeff = NULL, startTime = NULL, startTimeFormat = NULL, activityTimeFormat = NULL, matrixType = NULL) {
   stage <- mmlspark_amd$models$sar$SAR()
   if (!is.null(userCol)) stage$set("userCol", userCol)
   if (!is.null(itemCol)) stage$set("itemCol", itemCol)
@@ -1468,6 +1468,7 @@ ml_sar <- function(userCol = NULL, itemCol = NULL, ratingCol = NULL, timeCol = N
   if (!is.null(startTime)) stage$set("startTime", startTime)
   if (!is.null(startTimeFormat)) stage$set("startTimeFormat", startTimeFormat)
   if (!is.null(activityTimeFormat)) stage$set("activityTimeFormat", activityTimeFormat)
+  if (!is.null(matrixType)) stage$set("matrixType", matrixType)
   stage
 }
 

@@ -381,6 +381,165 @@ def knn_topk(Q, X, xsq, k, label_ids=None, allow_bits=None, splits=0):
                             int(splits))
 
 
+# ------------------------------------------------------------ recommendation
+SAR_MAX_K = 128        # sar_recommend_topk_k keeps 2k (score, item) pairs in LDS
+SAR_MAX_TILE = 16384   # LDS cells of one item tile
+SAR_SIMILARITY = {"cooccurrence": 0, "jaccard": 1, "lift": 2}
+
+
+def check_sar_csr(name, indptr, col, val, n_cols, structure=True):
+    """A CSR matrix as the sar kernels read it: int64 indptr (rows + 1),
+    int32 col, float32 val (None for a pattern), all contiguous and on one
+    device.  With `structure` also everything the kernels index with, in
+    O(nnz) on the device: indptr from 0 to nnz without decreasing, columns
+    inside [0, n_cols) and strictly increasing inside a row, values finite.
+    Raises ValueError; nothing is launched."""
+    def bad(msg):
+        raise ValueError("sar: %s %s" % (name, msg))
+
+    tensors = [("indptr", indptr, torch.int64), ("col", col, torch.int32)]
+    if val is not None:
+        tensors.append(("val", val, torch.float32))
+    for what, t, dt in tensors:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            bad("%s must be a %s tensor" % (what, str(dt).split(".")[-1]))
+        if t.dim() != 1 or not t.is_contiguous():
+            bad(what + " must be 1-D and contiguous")
+        if t.device != indptr.device:
+            bad(what + " must live where indptr lives")
+    if indptr.numel() < 1:
+        bad("indptr must hold rows + 1 entries")
+    if indptr.numel() - 1 >= (1 << 31) or int(n_cols) >= (1 << 31):
+        bad("must have fewer than 2^31 rows and columns")
+    if val is not None and val.numel() != col.numel():
+        bad("val must hold one value per column index")
+    if not structure:
+        return
+    nnz = col.numel()
+    if int(indptr[0]) != 0 or int(indptr[-1]) != nnz:
+        bad("indptr must start at 0 and end at nnz")
+    if indptr.numel() > 1 and bool((indptr[1:] < indptr[:-1]).any()):
+        bad("indptr must not decrease")
+    if nnz:
+        if int(col.min()) < 0 or int(col.max()) >= int(n_cols):
+            bad("columns must lie in [0, %d)" % int(n_cols))
+        rising = col[1:] > col[:-1]
+        starts = indptr[1:-1]
+        starts = starts[(starts > 0) & (starts < nnz)]
+        rising[starts - 1] = True
+        if not bool(rising.all()):
+            bad("columns must be strictly increasing inside a row")
+        if val is not None and not bool(torch.isfinite(val).all()):
+            bad("values must be finite")
+
+
+def _check_sar_tile(tile):
+    if int(tile) != tile or tile < 0 or tile % 64 or tile > SAR_MAX_TILE:
+        raise ValueError("sar: tile must be 0 (automatic) or a multiple of 64 "
+                         "up to %d" % SAR_MAX_TILE)
+    return int(tile)
+
+
+def _sar_fused(t) -> bool:
+    """GPU tensors go to sar_kernels.hip unless MMLSPARK_AMD_SAR_FUSED=0."""
+    import os
+    return t.is_cuda and os.environ.get("MMLSPARK_AMD_SAR_FUSED", "1") != "0"
+
+
+def sar_cooccurrence(b_indptr, b_col, bt_indptr, bt_col, threshold,
+                     similarity, tile=0, check=True):
+    """Item-item similarity of a binarised user-item CSR pattern B (users x
+    items) and its transpose Bt, as CSR (indptr int64, col int32 ascending,
+    val float32), symmetric, diagonal included.  c_ij = users holding both
+    items, occ_i = c_ii; an entry is kept iff c_ij >= max(threshold, 1).
+    similarity: "cooccurrence" (float)c, "jaccard" (float)c / (float)(occ_i +
+    occ_j - c), "lift" (float)c / ((float)occ_i * (float)occ_j), IEEE float32.
+    `tile` (a multiple of 64, 0 = automatic) is the item-tile width of the
+    device kernels; the result does not depend on it.  check=False skips the
+    O(nnz) structure check for patterns already checked."""
+    if similarity not in SAR_SIMILARITY:
+        raise ValueError("sar: similarity must be one of %s"
+                         % sorted(SAR_SIMILARITY))
+    tile = _check_sar_tile(tile)
+    n_users, n_items = b_indptr.numel() - 1, bt_indptr.numel() - 1
+    check_sar_csr("B", b_indptr, b_col, None, n_items, check)
+    check_sar_csr("Bt", bt_indptr, bt_col, None, n_users, check)
+    if bt_col.device != b_col.device or bt_col.numel() != b_col.numel():
+        raise ValueError("sar: B and Bt must hold the same entries on one "
+                         "device")
+    thr = min(max(int(threshold), 1), (1 << 31) - 1)
+    sim = SAR_SIMILARITY[similarity]
+    if _sar_fused(b_col):
+        return _require_ext().sar_cooccurrence(b_indptr, b_col, bt_indptr,
+                                               bt_col, thr, sim, tile)
+    return cpu_ref.sar_cooccurrence(b_indptr, b_col, bt_indptr, bt_col, thr,
+                                    sim, tile)
+
+
+def _check_sar_model(a_indptr, a_col, a_val, s_indptr, s_col, s_val, check):
+    n_items = s_indptr.numel() - 1
+    check_sar_csr("affinity", a_indptr, a_col, a_val, n_items, check)
+    check_sar_csr("similarity", s_indptr, s_col, s_val, n_items, check)
+    if s_col.device != a_col.device:
+        raise ValueError("sar: affinity and similarity must share a device")
+
+
+def _check_sar_ids(name, t, like):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise ValueError("sar: %s must be an int32 tensor" % name)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("sar: %s must be 1-D and contiguous" % name)
+    if t.device != like.device:
+        raise ValueError("sar: %s must live where the model lives" % name)
+
+
+def sar_recommend(a_indptr, a_col, a_val, s_indptr, s_col, s_val, users, k,
+                  remove_seen=True, tile=0, check=True):
+    """The k best items of every user in `users` ((n,) int32, repeats allowed;
+    None = every user) from CSR affinity (users x items) and similarity (items
+    x items): score(u, j) = sum_i a_ui * s_ij, ordered by (score descending,
+    item ascending).  Every item is a candidate, zero scores included, except,
+    with remove_seen, those whose affinity is > 0.  On the device a score is
+    the fmaf chain over the user's entries in ascending i from 0.0f, whatever
+    `tile` is.  k above SAR_MAX_K, CPU tensors and MMLSPARK_AMD_SAR_FUSED=0
+    take cpu_ref.sar_recommend.  Returns (items (n, k) int32, scores (n, k)
+    float32), (-1, -inf) in unused slots."""
+    if int(k) != k or k < 1:
+        raise ValueError("sar: k must be an integer >= 1")
+    tile = _check_sar_tile(tile)
+    _check_sar_model(a_indptr, a_col, a_val, s_indptr, s_col, s_val, check)
+    if users is not None:
+        _check_sar_ids("users", users, a_col)
+        n_users = a_indptr.numel() - 1
+        if users.numel() and (int(users.min()) < 0
+                              or int(users.max()) >= n_users):
+            raise ValueError("sar: users must lie in [0, %d)" % n_users)
+    if _sar_fused(a_col) and k <= SAR_MAX_K:
+        return _require_ext().sar_recommend(a_indptr, a_col, a_val, s_indptr,
+                                            s_col, s_val, users, int(k),
+                                            bool(remove_seen), tile)
+    return cpu_ref.sar_recommend(a_indptr, a_col, a_val, s_indptr, s_col,
+                                 s_val, users, int(k), bool(remove_seen), tile)
+
+
+def sar_score_pairs(a_indptr, a_col, a_val, s_indptr, s_col, s_val, users,
+                    items, check=True):
+    """score(users[p], items[p]) as sar_recommend defines it, float32 (n,);
+    on the device bit-equal to the score sar_recommend reports for that pair.
+    A pair with an id outside the model scores 0."""
+    _check_sar_model(a_indptr, a_col, a_val, s_indptr, s_col, s_val, check)
+    _check_sar_ids("users", users, a_col)
+    _check_sar_ids("items", items, a_col)
+    if users.numel() != items.numel():
+        raise ValueError("sar: users and items must pair up")
+    if _sar_fused(a_col):
+        return _require_ext().sar_score_pairs(a_indptr, a_col, a_val,
+                                              s_indptr, s_col, s_val, users,
+                                              items)
+    return cpu_ref.sar_score_pairs(a_indptr, a_col, a_val, s_indptr, s_col,
+                                   s_val, users, items)
+
+
 # ------------------------------------------------------------------- images
 JPEG_MAX_PIXELS = 1 << 26
 

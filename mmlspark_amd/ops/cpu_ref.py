@@ -651,3 +651,147 @@ def knn_topk_f64(Q, X, k, label_ids=None, allow_bits=None):
         return (diff * diff).sum(2)
     return _knn_run(Q, Xd, k, label_ids, allow_bits, dist, torch.float64,
                     X.shape[0] * X.shape[1])
+
+
+# ------------------------------------------------------------ recommendation
+# Sparse SAR in torch ops on whatever device the CSR arrays live on: the
+# contract of ops/hip/sar_kernels.hip (int64 indptr, int32 columns strictly
+# increasing per row, float32 values).
+def _csr_rows(indptr):
+    """Row index of every stored entry."""
+    n = indptr.numel() - 1
+    return torch.repeat_interleave(
+        torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1])
+
+
+def _expand_segments(starts, lengths):
+    """For segments (starts[s], lengths[s]): the owner s of every element and
+    its absolute position, segments in order."""
+    dev = starts.device
+    owner = torch.repeat_interleave(
+        torch.arange(lengths.numel(), device=dev), lengths)
+    first = torch.cumsum(lengths, 0) - lengths
+    pos = starts[owner] + (torch.arange(owner.numel(), device=dev)
+                           - first[owner])
+    return owner, pos
+
+
+def sar_cooccurrence(b_indptr, b_col, bt_indptr, bt_col, threshold, sim,
+                     tile=0):
+    """S = similarity(Bt.B) as CSR.  c_ij = users holding both items,
+    occ_i = c_ii; an entry is kept iff c_ij >= threshold (>= 1), diagonal
+    included.  sim 0: (float)c; 1 (jaccard): (float)c / (float)(occ_i + occ_j
+    - c); 2 (lift): (float)c / ((float)occ_i * (float)occ_j).  The pairs of
+    a chunk of users are enumerated and counted with torch.unique, so memory
+    follows sum(deg^2) of a chunk, never items^2.  `tile` only shapes the
+    device launch.  Returns (indptr int64, col int32, val float32)."""
+    dev = b_col.device
+    n_users, n_items = b_indptr.numel() - 1, bt_indptr.numel() - 1
+    deg = b_indptr[1:] - b_indptr[:-1]
+    occ = bt_indptr[1:] - bt_indptr[:-1]
+    csum = torch.cumsum(deg * deg, 0)
+    keys, cnts = [], []
+    lo = 0
+    while lo < n_users:
+        base = int(csum[lo - 1]) if lo else 0
+        hi = int(torch.searchsorted(csum, torch.tensor(base + (1 << 24),
+                                                       device=dev),
+                                    right=True))
+        hi = min(n_users, max(hi, lo + 1))
+        e = torch.arange(int(b_indptr[lo]), int(b_indptr[hi]), device=dev)
+        user = lo + _csr_rows(b_indptr[lo:hi + 1] - b_indptr[lo])
+        owner, pos = _expand_segments(b_indptr[user], deg[user])
+        key = b_col[e[owner]].long() * n_items + b_col[pos].long()
+        uk, c = torch.unique(key, return_counts=True)
+        keys.append(uk)
+        cnts.append(c)
+        lo = hi
+    if keys:
+        uk, inv = torch.unique(torch.cat(keys), return_inverse=True)
+        c = torch.zeros(uk.numel(), dtype=torch.int64, device=dev)
+        c.index_add_(0, inv, torch.cat(cnts))
+    else:
+        uk = torch.zeros(0, dtype=torch.int64, device=dev)
+        c = uk
+    keep = c >= max(int(threshold), 1)
+    uk, c = uk[keep], c[keep]
+    i, j = uk // max(n_items, 1), uk % max(n_items, 1)
+    val = c.float()
+    if sim == 1:
+        val = val / (occ[i] + occ[j] - c).float()
+    elif sim == 2:
+        val = val / (occ[i].float() * occ[j].float())
+    indptr = torch.zeros(n_items + 1, dtype=torch.int64, device=dev)
+    indptr[1:] = torch.cumsum(torch.bincount(i, minlength=n_items), 0)
+    return indptr, j.to(torch.int32), val
+
+
+def sar_recommend(a_indptr, a_col, a_val, s_indptr, s_col, s_val, users, k,
+                  remove_seen=True, tile=0):
+    """Top-k items of every requested user (all when `users` is None) under
+    the total order (score descending, item ascending).  score(u, j) = sum
+    over u's stored entries i of a_ui * s_ij, float32; with remove_seen the
+    items whose affinity is > 0 are no candidates, every other item is, zero
+    scores included.  Users are scored in chunks densified by index_add_
+    (its order of addition is torch's, not the kernel's ascending-i fmaf
+    chain).  Returns (items (n, k) int32, scores (n, k) float32) with
+    (-1, -inf) in unused slots."""
+    dev = a_col.device
+    n_users, n_items = a_indptr.numel() - 1, s_indptr.numel() - 1
+    rows = (torch.arange(n_users, device=dev) if users is None
+            else users.long())
+    n = rows.numel()
+    out_i = torch.full((n, k), -1, dtype=torch.int32, device=dev)
+    out_s = torch.full((n, k), float("-inf"), dtype=torch.float32, device=dev)
+    if n == 0 or n_items == 0:
+        return out_i, out_s
+    s_len = s_indptr[1:] - s_indptr[:-1]
+    kk = min(k, n_items)
+    step = max(1, (1 << 24) // n_items)
+    for lo in range(0, n, step):
+        r = rows[lo:lo + step]
+        m = r.numel()
+        own, e = _expand_segments(a_indptr[r], a_indptr[r + 1] - a_indptr[r])
+        it, av = a_col[e].long(), a_val[e]
+        own2, q = _expand_segments(s_indptr[it], s_len[it])
+        sc = torch.zeros(m * n_items, dtype=torch.float32, device=dev)
+        sc.index_add_(0, own[own2] * n_items + s_col[q].long(),
+                      av[own2] * s_val[q])
+        if remove_seen:
+            seen = av > 0
+            sc[own[seen] * n_items + it[seen]] = float("-inf")
+        srt, order = torch.sort(sc.view(m, n_items), dim=1, descending=True,
+                                stable=True)
+        srt, order = srt[:, :kk], order[:, :kk]
+        gone = torch.isinf(srt) & (srt < 0)
+        out_s[lo:lo + m, :kk] = srt
+        out_i[lo:lo + m, :kk] = torch.where(
+            gone, torch.full_like(order, -1), order).to(torch.int32)
+    return out_i, out_s
+
+
+def sar_score_pairs(a_indptr, a_col, a_val, s_indptr, s_col, s_val, users,
+                    items):
+    """score(u, i) of sar_recommend for every (users[p], items[p]); a pair
+    with an id out of range scores 0.  float32 (n,)."""
+    dev = a_col.device
+    n_users, n_items = a_indptr.numel() - 1, s_indptr.numel() - 1
+    out = torch.zeros(users.numel(), dtype=torch.float32, device=dev)
+    u, i = users.long(), items.long()
+    idx = torch.nonzero((u >= 0) & (u < n_users) & (i >= 0) & (i < n_items)
+                        ).flatten()
+    if idx.numel() == 0 or s_col.numel() == 0:
+        return out
+    skey = _csr_rows(s_indptr) * n_items + s_col.long()
+    step = 1 << 20
+    for lo in range(0, idx.numel(), step):
+        sel = idx[lo:lo + step]
+        uu, ii = u[sel], i[sel]
+        own, e = _expand_segments(a_indptr[uu], a_indptr[uu + 1] - a_indptr[uu])
+        want = ii[own] * n_items + a_col[e].long()
+        pos = torch.searchsorted(skey, want).clamp_(max=skey.numel() - 1)
+        hit = skey[pos] == want
+        part = torch.zeros(sel.numel(), dtype=torch.float32, device=dev)
+        part.index_add_(0, own[hit], a_val[e][hit] * s_val[pos[hit]])
+        out[sel] = part
+    return out

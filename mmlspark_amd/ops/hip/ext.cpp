@@ -83,6 +83,18 @@ int knn_choose_splits(long, long, int, int);
 int launch_knn_topk(const float*, const float*, const float*, const float*,
                     const int*, const unsigned*, long, long, int, int, int,
                     int, float*, int*, float*, int*, hipStream_t);
+int sar_default_tile(long, int);
+int launch_sar_cooc_count(const long*, const int*, const long*, const int*,
+                          int, int, int, unsigned, int*, hipStream_t);
+int launch_sar_cooc_fill(const long*, const int*, const long*, const int*, int,
+                         int, int, unsigned, int, const long*, long, int*,
+                         float*, hipStream_t);
+int launch_sar_recommend(const long*, const int*, const float*, const long*,
+                         const int*, const float*, const int*, long, int, int,
+                         int, int, int, float*, int*, hipStream_t);
+int launch_sar_score_pairs(const long*, const int*, const float*, const long*,
+                           const int*, const float*, const int*, const int*,
+                           long, int, int, float*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -743,6 +755,148 @@ std::tuple<torch::Tensor, torch::Tensor> knn_topk(
   return {d2, idx};
 }
 
+// ------------------------------------------------------------ recommendation
+// sar_kernels.hip.  CSR structure (sorted columns, indptr monotone) is checked
+// by the caller (ops/backend.py); shapes, dtypes and ranges of scalars here.
+static const int kSarMaxK = 128;
+static const int kSarMaxTile = 16384;
+
+static void sar_check_csr(const torch::Tensor& indptr, const torch::Tensor& col,
+                          const torch::Tensor* val, const char* name) {
+  CHECK_DEV(indptr); CHECK_CONTIG(indptr);
+  CHECK_DEV(col); CHECK_CONTIG(col);
+  TORCH_CHECK(indptr.dtype() == torch::kInt64 && indptr.dim() == 1 &&
+              indptr.numel() >= 1, name, " indptr must be (rows + 1,) int64");
+  TORCH_CHECK(col.dtype() == torch::kInt32 && col.dim() == 1, name,
+              " col must be int32");
+  if (val != nullptr) {
+    CHECK_DEV((*val)); CHECK_CONTIG((*val));
+    TORCH_CHECK(val->dtype() == torch::kFloat32 && val->dim() == 1 &&
+                val->numel() == col.numel(), name,
+                " val must be float32, one per column");
+  }
+}
+
+static int sar_tile(long tile, long n_items, int which) {
+  TORCH_CHECK(tile >= 0 && tile <= kSarMaxTile && tile % 64 == 0,
+              "tile must be 0 or a multiple of 64 up to ", kSarMaxTile);
+  return tile == 0 ? sar_default_tile(n_items, which) : (int)tile;
+}
+
+// Sparse Bt.B with threshold and similarity fused: (indptr, col, val) of S.
+// sim: 0 cooccurrence, 1 jaccard, 2 lift.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> sar_cooccurrence(
+    torch::Tensor b_indptr, torch::Tensor b_col, torch::Tensor bt_indptr,
+    torch::Tensor bt_col, long threshold, long sim, long tile) {
+  sar_check_csr(b_indptr, b_col, nullptr, "B");
+  sar_check_csr(bt_indptr, bt_col, nullptr, "Bt");
+  const long n_users = b_indptr.numel() - 1, n_items = bt_indptr.numel() - 1;
+  TORCH_CHECK(n_users < (1L << 31) && n_items < (1L << 31),
+              "too many users or items");
+  TORCH_CHECK(sim >= 0 && sim <= 2, "unknown similarity function");
+  TORCH_CHECK(threshold >= 1 && threshold < (1L << 31), "threshold out of range");
+  const int T = sar_tile(tile, n_items, 0);
+  const long n_tiles = (n_items + T - 1) / T;
+  TORCH_CHECK(n_tiles <= 65535, "too many item tiles: use a wider tile");
+  auto iopt = b_col.options();
+  if (n_items == 0)
+    return {torch::zeros({1}, b_indptr.options()), torch::empty({0}, iopt),
+            torch::empty({0}, iopt.dtype(torch::kFloat32))};
+  auto counts = torch::empty({n_items * n_tiles}, iopt);
+  int err = launch_sar_cooc_count(
+      bt_indptr.data_ptr<long>(), bt_col.data_ptr<int>(),
+      b_indptr.data_ptr<long>(), b_col.data_ptr<int>(), (int)n_users,
+      (int)n_items, T, (unsigned)threshold, counts.data_ptr<int>(),
+      cur_stream());
+  TORCH_CHECK(err == 0, "sar_cooc_count launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  auto incl = counts.cumsum(0, torch::kInt64);
+  auto offsets = (incl - counts).contiguous();
+  const long nnz = incl[-1].item<long>();
+  auto indptr = torch::cat({offsets.slice(0, 0, n_items * n_tiles, n_tiles),
+                            incl.slice(0, n_items * n_tiles - 1)});
+  auto col = torch::empty({nnz}, iopt);
+  auto val = torch::empty({nnz}, iopt.dtype(torch::kFloat32));
+  if (nnz > 0) {
+    err = launch_sar_cooc_fill(
+        bt_indptr.data_ptr<long>(), bt_col.data_ptr<int>(),
+        b_indptr.data_ptr<long>(), b_col.data_ptr<int>(), (int)n_users,
+        (int)n_items, T, (unsigned)threshold, (int)sim,
+        offsets.data_ptr<long>(), nnz, col.data_ptr<int>(),
+        val.data_ptr<float>(), cur_stream());
+    TORCH_CHECK(err == 0, "sar_cooc_fill launch failed: ",
+                hipGetErrorString((hipError_t)err));
+  }
+  return {indptr.contiguous(), col, val};
+}
+
+// Top-k items per requested user: (items (n, k) int32, scores (n, k) float32)
+std::tuple<torch::Tensor, torch::Tensor> sar_recommend(
+    torch::Tensor a_indptr, torch::Tensor a_col, torch::Tensor a_val,
+    torch::Tensor s_indptr, torch::Tensor s_col, torch::Tensor s_val,
+    c10::optional<torch::Tensor> users, long k, bool remove_seen, long tile) {
+  sar_check_csr(a_indptr, a_col, &a_val, "affinity");
+  sar_check_csr(s_indptr, s_col, &s_val, "similarity");
+  const long n_users = a_indptr.numel() - 1, n_items = s_indptr.numel() - 1;
+  TORCH_CHECK(n_users < (1L << 31) && n_items < (1L << 31),
+              "too many users or items");
+  TORCH_CHECK(k >= 1 && k <= kSarMaxK, "k out of range");
+  const int T = sar_tile(tile, n_items, 1);
+  const int* up = nullptr;
+  long n = n_users;
+  if (users.has_value()) {
+    const auto& u = *users;
+    CHECK_DEV(u); CHECK_CONTIG(u);
+    TORCH_CHECK(u.dtype() == torch::kInt32 && u.dim() == 1,
+                "users must be (n,) int32");
+    up = u.data_ptr<int>();
+    n = u.numel();
+  }
+  TORCH_CHECK(n < (1L << 31), "too many users for one launch");
+  auto scores = torch::empty({n, k}, a_val.options());
+  auto items = torch::empty({n, k}, a_col.options());
+  if (n == 0) return {items, scores};
+  const int err = launch_sar_recommend(
+      a_indptr.data_ptr<long>(), a_col.data_ptr<int>(),
+      a_val.data_ptr<float>(), s_indptr.data_ptr<long>(),
+      s_col.data_ptr<int>(), s_val.data_ptr<float>(), up, n, (int)n_users,
+      (int)n_items, T, (int)k, remove_seen ? 1 : 0, scores.data_ptr<float>(),
+      items.data_ptr<int>(), cur_stream());
+  TORCH_CHECK(err == 0, "sar_recommend launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return {items, scores};
+}
+
+torch::Tensor sar_score_pairs(
+    torch::Tensor a_indptr, torch::Tensor a_col, torch::Tensor a_val,
+    torch::Tensor s_indptr, torch::Tensor s_col, torch::Tensor s_val,
+    torch::Tensor users, torch::Tensor items) {
+  sar_check_csr(a_indptr, a_col, &a_val, "affinity");
+  sar_check_csr(s_indptr, s_col, &s_val, "similarity");
+  CHECK_DEV(users); CHECK_CONTIG(users);
+  CHECK_DEV(items); CHECK_CONTIG(items);
+  TORCH_CHECK(users.dtype() == torch::kInt32 && items.dtype() == torch::kInt32 &&
+              users.dim() == 1 && items.dim() == 1 &&
+              users.numel() == items.numel(),
+              "users and items must be (n,) int32");
+  const long n_users = a_indptr.numel() - 1, n_items = s_indptr.numel() - 1;
+  TORCH_CHECK(n_users < (1L << 31) && n_items < (1L << 31),
+              "too many users or items");
+  const long n = users.numel();
+  TORCH_CHECK(n < (1L << 39), "too many pairs for one launch");
+  auto out = torch::empty({n}, a_val.options());
+  if (n == 0) return out;
+  const int err = launch_sar_score_pairs(
+      a_indptr.data_ptr<long>(), a_col.data_ptr<int>(),
+      a_val.data_ptr<float>(), s_indptr.data_ptr<long>(),
+      s_col.data_ptr<int>(), s_val.data_ptr<float>(), users.data_ptr<int>(),
+      items.data_ptr<int>(), n, (int)n_users, (int)n_items,
+      out.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(err == 0, "sar_score_pairs launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -782,4 +936,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused exact k-nearest-neighbour search with optional label bitsets");
   m.attr("KNN_MAX_K") = kKnnMaxK;
   m.attr("KNN_MAX_SPLITS") = kKnnMaxSplits;
+  m.def("sar_cooccurrence", &sar_cooccurrence,
+        "sparse item-item co-occurrence with threshold and similarity fused");
+  m.def("sar_recommend", &sar_recommend,
+        "fused SAR scoring + exact top-k per user over CSR affinity/similarity");
+  m.def("sar_score_pairs", &sar_score_pairs,
+        "SAR score of (user, item) pairs, bit-equal to sar_recommend's");
+  m.def("sar_default_tile", &sar_default_tile,
+        "tile the SAR launchers pick (which: 0 co-occurrence, 1 recommend)");
+  m.attr("SAR_MAX_K") = kSarMaxK;
+  m.attr("SAR_MAX_TILE") = kSarMaxTile;
 }

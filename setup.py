@@ -20,7 +20,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 
 KERNEL_SOURCES = ["gbdt_kernels.hip", "vw_kernels.hip",
                   "image_kernels.hip", "rank_kernels.hip",
-                  "knn_kernels.hip"]
+                  "knn_kernels.hip", "sar_kernels.hip"]
 
 
 def compile_hip_kernels():
