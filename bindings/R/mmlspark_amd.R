@@ -699,7 +699,7 @@ ml_identify_faces <- function(url = NULL, subscriptionKey = NULL, subscriptionKe
   stage
 }
 
-ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = NULL, moduleBytes = NULL, device = NULL, modelName = NULL, cutOutputLayers = NULL, imageSize = NULL, modelPath = NULL, decodeOnDevice = NULL) {
+ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = NULL, moduleBytes = NULL, device = NULL, modelName = NULL, cutOutputLayers = NULL, imageSize = NULL, modelPath = NULL, decodeOnDevice = NULL, fusedPreprocess = NULL) {
   stage <- mmlspark_amd$models$image_featurizer$ImageFeaturizer()
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(outputCol)) stage$set("outputCol", outputCol)
@@ -711,6 +711,7 @@ ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = N
   if (!is.null(imageSize)) stage$set("imageSize", imageSize)
   if (!is.null(modelPath)) stage$set("modelPath", modelPath)
   if (!is.null(decodeOnDevice)) stage$set("decodeOnDevice", decodeOnDevice)
+  if (!is.null(fusedPreprocess)) stage$set("fusedPreprocess", fusedPreprocess)
   stage
 }
 
@@ -767,12 +768,13 @@ ml_image_set_augmenter <- function(inputCol = NULL, outputCol = NULL, flipLeftRi
   stage
 }
 
-ml_image_transformer <- function(inputCol = NULL, outputCol = NULL, stages = NULL, outputType = NULL) {
+ml_image_transformer <- function(inputCol = NULL, outputCol = NULL, stages = NULL, outputType = NULL, fused = NULL) {
   stage <- mmlspark_amd$models$images$ImageTransformer()
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(outputCol)) stage$set("outputCol", outputCol)
   if (!is.null(stages)) stage$set("stages", stages)
   if (!is.null(outputType)) stage$set("outputType", outputType)
+  if (!is.null(fused)) stage$set("fused", fused)
   stage
 }
 
@@ -1447,12 +1449,13 @@ ml_repartition <- function(n = NULL, disable = NULL) {
   stage
 }
 
-ml_resize_image_transformer <- function(inputCol = NULL, outputCol = NULL, height = NULL, width = NULL) {
+ml_resize_image_transformer <- function(inputCol = NULL, outputCol = NULL, height = NULL, width = NULL, fused = NULL) {
   stage <- mmlspark_amd$models$images$ResizeImageTransformer()
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(outputCol)) stage$set("outputCol", outputCol)
   if (!is.null(height)) stage$set("height", height)
   if (!is.null(width)) stage$set("width", width)
+  if (!is.null(fused)) stage$set("fused", fused)
   stage
 }
 

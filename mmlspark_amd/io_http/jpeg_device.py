@@ -39,10 +39,24 @@ def decode_jpeg_batch(blobs: Sequence[bytes], device,
     ``device="cpu"`` runs the same export, packing and descriptor check and
     reconstructs with the torch reference.  Malformed or unsupported streams
     raise ``ValueError`` (like ``jpeg_codec.decode_jpeg``)."""
+    out, spans = decode_jpeg_batch_flat(blobs, device, num_threads)
+    res = []
+    for off, shape in spans:
+        numel = shape[0] * shape[1] * (3 if len(shape) == 3 else 1)
+        res.append(out[off:off + numel].view(shape))
+    return res
+
+
+def decode_jpeg_batch_flat(blobs: Sequence[bytes], device,
+                           num_threads: int = 16):
+    """The allocation behind ``decode_jpeg_batch``: (flat uint8 buffer on
+    ``device``, [(offset, shape), ...]) with image i's pixels, HWC, at its
+    dword-aligned offset — what ``ops.backend.image_preprocess`` reads
+    without a copy."""
     device = torch.device(device)
     n = len(blobs)
     if n == 0:
-        return []
+        return torch.empty(0, dtype=torch.uint8, device=device), []
     workers = max(1, min(int(num_threads), _MAX_THREADS, n))
     try:
         if workers == 1:
@@ -98,8 +112,4 @@ def decode_jpeg_batch(blobs: Sequence[bytes], device,
     if pin:
         qt, coef = views(stage.to(device, non_blocking=True))
     backend.jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off, out)
-    res = []
-    for off, shape in spans:
-        numel = shape[0] * shape[1] * (3 if len(shape) == 3 else 1)
-        res.append(out[off:off + numel].view(shape))
-    return res
+    return out, spans

@@ -115,6 +115,28 @@ def _jpeg_rows_to_device_batch(vals, size: int, device) -> torch.Tensor:
     return torch.cat([to_unit_nchw(t.unsqueeze(0)) for t in imgs])
 
 
+def _jpeg_rows_to_device_batch_fused(vals, size: int, device) -> torch.Tensor:
+    """JPEG byte cells -> (N,3,size,size) f32 on `device` in two launches:
+    the decode, then ONE image_preprocess launch that reads the decoder's
+    flat allocation and does resize to size², gray replicated to three
+    channels, ÷ 255 and the CHW layout — no per-image op and no stack."""
+    from ..io_http.jpeg_device import decode_jpeg_batch_flat
+    from ..ops import backend
+    from .images import compile_image_plan
+    flat, spans = decode_jpeg_batch_flat([bytes(v) for v in vals], device)
+    shapes = [(s[0], s[1], 3 if len(s) == 3 else 1) for _, s in spans]
+    plan = compile_image_plan(
+        [{"op": "resize", "height": size, "width": size},
+         {"op": "colorFormat", "format": "_replicate3"},
+         {"op": "normalize", "mean": [0.0], "std": [1.0]}],
+        shapes, "uint8", "float32", "CHW", src_off=[o for o, _ in spans])
+    if plan is None:
+        raise ValueError("image batch does not fit the fused preprocess plan")
+    out = torch.empty(plan.out_numel, dtype=torch.float32, device=device)
+    backend.image_preprocess(flat, plan.idesc, plan.fdesc, plan.work_off, out)
+    return out.view(len(vals), 3, size, size)
+
+
 @register
 class TorchModel(Model):
     """Generic batched torch-module inference transformer (CNTKModel analog).
@@ -200,6 +222,10 @@ class ImageFeaturizer(TorchModel):
                            "decode JPEG byte cells on the GPU (host Huffman "
                            "decode, device dequant/IDCT/colour) when the "
                            "stage runs on a CUDA device", False, toBool)
+    fusedPreprocess = Param("fusedPreprocess",
+                            "with decodeOnDevice: resize, gray->3 channels, "
+                            "÷255 and the NCHW layout of the whole decoded "
+                            "batch in one fused kernel launch", False, toBool)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -229,6 +255,9 @@ class ImageFeaturizer(TorchModel):
                     isinstance(v, (bytes, bytearray, memoryview))
                     and bytes(v[:2]) == b"\xff\xd8" for v in vals):
                 try:
+                    if self.get("fusedPreprocess"):
+                        return _jpeg_rows_to_device_batch_fused(
+                            vals, size, device)
                     return _jpeg_rows_to_device_batch(vals, size, device)
                 except ValueError:
                     # a stream the device path rejects: this batch takes the

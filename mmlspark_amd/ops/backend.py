@@ -640,3 +640,120 @@ def jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off, out):
         return out
     return cpu_ref.jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off,
                                     out)
+
+
+IMG_TILE_W, IMG_TILE_H = 64, 8          # image_preprocess_k's output tile
+IMG_DESC_I, IMG_DESC_F = cpu_ref.IMG_DESC_I, cpu_ref.IMG_DESC_F
+IMG_MAX_DIM = 32768
+
+
+def image_work_items(Ho, Wo):
+    """Work items (workgroups) image_preprocess_k spends on one Ho x Wo
+    output: tiles of 64 x 8 pixels.  Works on ints and arrays."""
+    return (((Wo + IMG_TILE_W - 1) // IMG_TILE_W)
+            * ((Ho + IMG_TILE_H - 1) // IMG_TILE_H))
+
+
+def check_image_descriptors(src, idesc, fdesc, work_off, out):
+    """Validate a batch's plan against the buffers — everything
+    image_preprocess_k indexes with (descriptor layout in
+    image_kernels.hip).  O(N) on CPU tensors; raises ValueError and nothing
+    is launched.  Runs before the GPU launch and before the CPU reference
+    alike."""
+    import numpy as np
+
+    def bad(msg):
+        raise ValueError("image_preprocess: " + msg)
+
+    for name, t in (("src", src), ("out", out)):
+        if t.dtype not in (torch.uint8, torch.float32) or t.dim() != 1 \
+                or not t.is_contiguous():
+            bad(name + " must be a flat contiguous uint8 or float32 buffer")
+    if src.device != out.device:
+        bad("src and out must share a device")
+    for name, t, dt in (("idesc", idesc, torch.int64),
+                        ("fdesc", fdesc, torch.float32),
+                        ("work_off", work_off, torch.int64)):
+        if t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            bad(name + " must be a contiguous CPU %s tensor"
+                % str(dt).replace("torch.", ""))
+    n = idesc.shape[0] if idesc.dim() == 2 else -1
+    if (n < 0 or tuple(idesc.shape) != (n, IMG_DESC_I)
+            or tuple(fdesc.shape) != (n, IMG_DESC_F)
+            or tuple(work_off.shape) != (n + 1,)):
+        bad("descriptor shapes do not agree on the batch size")
+    if n == 0:
+        return
+    d, f, wo = idesc.numpy(), fdesc.numpy(), work_off.numpy()
+    (src_off, Hs, Ws, Cs, py0, px0, Hc, Wc, flags, Hr, Wr, qy0, qx0, Ho, Wo,
+     Co, cmap, gmap, out_off, n_ops, kinds) = (d[:, k] for k in range(21))
+    dims = np.stack([Hs, Ws, Hc, Wc, Hr, Wr, Ho, Wo])
+    if ((dims < 1) | (dims > IMG_MAX_DIM)).any():
+        bad("image dimension outside 1..%d" % IMG_MAX_DIM)
+    if ((Cs < 1) | (Cs > 4) | (Co < 1) | (Co > 4)).any():
+        bad("channel count outside 1..4")
+    if ((flags < 0) | (flags > 63)).any() or (d[:, 21:] != 0).any():
+        bad("unknown flag bits")
+    if ((src_off < 0) | (src_off + Hs * Ws * Cs > src.numel())).any():
+        bad("source image runs past the source buffer")
+    if ((py0 < 0) | (px0 < 0) | (py0 + Hc > Hs) | (px0 + Wc > Ws)).any():
+        bad("pre-window outside its source image")
+    rs = (flags & 16) != 0
+    if ((~rs) & ((Hr != Hc) | (Wr != Wc))).any():
+        bad("copy path needs the resized size to equal the pre-window's")
+    sy = Hc.astype(np.float32) / Hr.astype(np.float32)
+    sx = Wc.astype(np.float32) / Wr.astype(np.float32)
+    if (rs & ((f[:, 0] != sy) | (f[:, 1] != sx))).any():
+        bad("scale is not float32(n_in) / float32(n_out)")
+    if ((qy0 < 0) | (qx0 < 0) | (qy0 + Ho > Hr) | (qx0 + Wo > Wr)).any():
+        bad("post-window outside the resized image")
+    uses_gray = np.zeros(n, bool)
+    for k in range(4):
+        code = (cmap >> (8 * k)) & 0xff
+        used = Co > k
+        uses_gray |= used & (code == 4)
+        if (used & (code != 4) & (code >= Cs)).any() \
+                or (~used & (code != 0)).any():
+            bad("channel map names a channel the source does not have")
+    if ((cmap < 0) | (cmap >= 1 << 32) | (gmap < 0) | (gmap >= 1 << 24)).any():
+        bad("channel map names a channel the source does not have")
+    for k in range(3):
+        if (uses_gray & (((gmap >> (8 * k)) & 0xff) >= Cs)).any():
+            bad("channel map names a channel the source does not have")
+    if ((n_ops < 0) | (n_ops > 4) | (kinds < 0) | (kinds >= 1 << 32)).any():
+        bad("bad pointwise op table")
+    for j in range(4):
+        kind = (kinds >> (8 * j)) & 0xff
+        if ((n_ops > j) & (kind > 5)).any() or ((n_ops <= j) & (kind != 0)).any():
+            bad("bad pointwise op table")
+    size = Ho * Wo * Co
+    if ((out_off < 0) | (out_off + size > out.numel())).any():
+        bad("output image runs past the output buffer")
+    if ((out_off * out.element_size()) % 4 != 0).any():
+        bad("output image does not start on a dword")
+    order = np.argsort(out_off, kind="stable")
+    if (out_off[order][1:] < (out_off + size)[order][:-1]).any():
+        bad("output images overlap")
+    if wo[0] != 0 or (np.diff(wo) != image_work_items(Ho, Wo)).any():
+        bad("work_off is not the prefix sum of the per-image work items")
+    if wo[-1] >= (1 << 31):
+        bad("batch too large for one launch")
+
+
+def image_preprocess(src, idesc, fdesc, work_off, out):
+    """Run a compiled image plan (models/images.py::compile_image_plan) over
+    the flat source buffer `src` into the flat buffer `out`, one launch for
+    the whole batch.  src / out are uint8 or float32 and share a device; the
+    descriptor tensors are CPU tensors: they are checked against the buffers
+    here, then copied to the device.  Pin them to make that copy
+    asynchronous."""
+    check_image_descriptors(src, idesc, fdesc, work_off, out)
+    if out.is_cuda:
+        ext = _require_ext()
+        dev = out.device
+        ext.image_preprocess(
+            src, idesc.to(dev, non_blocking=True),
+            fdesc.to(dev, non_blocking=True),
+            work_off.to(dev, non_blocking=True), int(work_off[-1]), out)
+        return out
+    return cpu_ref.image_preprocess(src, idesc, fdesc, work_off, out)

@@ -513,6 +513,95 @@ def jpeg_reconstruct(coef, qt, img_desc, comp_desc, work_off, out):
     return out
 
 
+IMG_DESC_I = 24
+IMG_DESC_F = 34
+IMG_OP_KINDS = ("binary", "binary_inv", "trunc", "tozero", "tozero_inv",
+                "normalize")
+
+
+def _image_axis(dst, scale, n_in: int):
+    """Taps and weights of destination indices `dst` on an axis resized
+    from n_in samples with `scale` = f32(n_in) / f32(n_out): every step is
+    its own rounded float32 operation, in image_preprocess_k's order."""
+    import numpy as np
+    half = np.float32(0.5)
+    src = np.float32(scale) * (dst.astype(np.float32) + half) - half
+    src = np.where(src < 0, np.float32(0), src).astype(np.float32)
+    i0 = np.clip(np.floor(src).astype(np.int64), 0, n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    l1 = src - i0.astype(np.float32)
+    l0 = np.float32(1.0) - l1
+    return i0, i1, l0, l1
+
+
+def image_preprocess(src, idesc, fdesc, work_off, out):
+    """Crop / flip / bilinear resize / channel map / threshold / normalize /
+    layout of a ragged image batch into `out` — numpy float32 in the order
+    of the contract in docs/kernels.md, so the result has the bits
+    image_preprocess_k writes.  Descriptor layout as in image_kernels.hip;
+    work_off is the kernel's scheduling table and is not needed here."""
+    import numpy as np
+    s_all, o_all = src.numpy(), out.numpy()
+    D, F = idesc.numpy(), fdesc.numpy()
+    as_u8 = o_all.dtype == np.uint8
+    for i in range(D.shape[0]):
+        d, f = [int(t) for t in D[i]], F[i]
+        src_off, Hs, Ws, Cs, py0, px0, Hc, Wc, flags = d[:9]
+        qy0, qx0, Ho, Wo, Co, cmap, gmap, out_off, n_ops, kinds = d[11:21]
+        img = s_all[src_off:src_off + Hs * Ws * Cs].reshape(Hs, Ws, Cs)
+        ox, oy = np.arange(Wo), np.arange(Ho)
+        rx = qx0 + (Wo - 1 - ox if flags & 4 else ox)
+        ry = qy0 + (Ho - 1 - oy if flags & 8 else oy)
+
+        def to_src(iy, ix):
+            sy = py0 + (Hc - 1 - iy if flags & 2 else iy)
+            sx = px0 + (Wc - 1 - ix if flags & 1 else ix)
+            return img[sy[:, None], sx[None, :], :].astype(np.float32)
+
+        if flags & 16:
+            y0, y1, l0y, l1y = _image_axis(ry, f[0], Hc)
+            x0, x1, l0x, l1x = _image_axis(rx, f[1], Wc)
+            l0x, l1x = l0x[None, :, None], l1x[None, :, None]
+            l0y, l1y = l0y[:, None, None], l1y[:, None, None]
+            top = l0x * to_src(y0, x0) + l1x * to_src(y0, x1)
+            bot = l0x * to_src(y1, x0) + l1x * to_src(y1, x1)
+            s = l0y * top + l1y * bot
+        else:
+            s = to_src(ry, rx)
+        codes = [(cmap >> (8 * k)) & 0xff for k in range(Co)]
+        gray = None
+        if 4 in codes:
+            c0, c1, c2 = (s[:, :, (gmap >> (8 * k)) & 3] for k in range(3))
+            gray = ((np.float32(0.299) * c2 + np.float32(0.587) * c1)
+                    + np.float32(0.114) * c0)
+        v = np.stack([gray if c >= 4 else s[:, :, c] for c in codes], axis=2)
+        zero = np.float32(0)
+        for j in range(n_ops):
+            kind = (kinds >> (8 * j)) & 0xff
+            q = f[2 + 8 * j:10 + 8 * j]
+            thr, mx = q[0], q[1]
+            if kind == 0:
+                v = np.where(v > thr, mx, zero)
+            elif kind == 1:
+                v = np.where(v > thr, zero, mx)
+            elif kind == 2:
+                v = np.minimum(v, thr)
+            elif kind == 3:
+                v = np.where(v > thr, v, zero)
+            elif kind == 4:
+                v = np.where(v > thr, zero, v)
+            elif kind == 5:
+                v = (v / np.float32(255.0) - q[None, None, :Co]) \
+                    / q[None, None, 4:4 + Co]
+            v = v.astype(np.float32, copy=False)
+        if as_u8:
+            v = np.clip(v, 0, 255).astype(np.uint8)
+        if flags & 32:
+            v = v.transpose(2, 0, 1)
+        o_all[out_off:out_off + Ho * Wo * Co] = v.reshape(-1)
+    return out
+
+
 # ------------------------------------------------------------------ ranking
 def group_rank(score: torch.Tensor, offsets: torch.Tensor, gid: torch.Tensor,
                label: torch.Tensor, gain: torch.Tensor,

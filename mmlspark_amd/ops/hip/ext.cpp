@@ -73,6 +73,10 @@ void launch_csr_partition(const long*, const int*, const unsigned char*,
 void launch_jpeg_reconstruct(const short*, const unsigned short*, const long*,
                              const long*, const long*, int, long,
                              unsigned char*, hipStream_t);
+long image_work_items(long, long);
+void launch_image_preprocess(const void*, long, int, const long*, const float*,
+                             const long*, int, long, void*, long, int,
+                             hipStream_t);
 void launch_group_rank(const float*, const long*, const int*, const float*,
                        const float*, const float*, long, int, long, int*,
                        void*, hipStream_t);
@@ -618,6 +622,46 @@ void jpeg_reconstruct(torch::Tensor coef, torch::Tensor qt,
       n_items, out.data_ptr<uint8_t>(), cur_stream());
 }
 
+// Fused crop / flip / resize / channel map / pointwise ops / layout of a
+// ragged image batch in one launch (image_preprocess_k), written into `out`
+// in place.  The descriptors must already have passed
+// ops/backend.py::check_image_descriptors; this checks the tensors against
+// the kernel's pointer types, and the kernel range-checks every index again.
+void image_preprocess(torch::Tensor src, torch::Tensor idesc,
+                      torch::Tensor fdesc, torch::Tensor work_off,
+                      long n_items, torch::Tensor out) {
+  CHECK_DEV(src); CHECK_CONTIG(src);
+  CHECK_DEV(idesc); CHECK_CONTIG(idesc);
+  CHECK_DEV(fdesc); CHECK_CONTIG(fdesc);
+  CHECK_DEV(work_off); CHECK_CONTIG(work_off);
+  CHECK_DEV(out); CHECK_CONTIG(out);
+  TORCH_CHECK(src.dtype() == torch::kUInt8 || src.dtype() == torch::kFloat32,
+              "src must be uint8 or float32");
+  TORCH_CHECK(out.dtype() == torch::kUInt8 || out.dtype() == torch::kFloat32,
+              "out must be uint8 or float32");
+  TORCH_CHECK(idesc.dtype() == torch::kInt64 &&
+              work_off.dtype() == torch::kInt64,
+              "idesc and work_off must be int64");
+  TORCH_CHECK(fdesc.dtype() == torch::kFloat32, "fdesc must be float32");
+  TORCH_CHECK(src.get_device() == out.get_device() &&
+              idesc.get_device() == out.get_device() &&
+              fdesc.get_device() == out.get_device() &&
+              work_off.get_device() == out.get_device(),
+              "all tensors must share one device");
+  const long n_img = idesc.dim() == 2 ? idesc.size(0) : -1;
+  TORCH_CHECK(n_img >= 0 && idesc.numel() == n_img * 24 &&
+              fdesc.numel() == n_img * 34 && work_off.numel() == n_img + 1,
+              "descriptor shapes do not agree on the batch size");
+  TORCH_CHECK(n_img < (1L << 31) && n_items >= 0 && n_items < (1L << 31),
+              "batch too large for one launch");
+  if (n_img == 0 || n_items == 0) return;
+  launch_image_preprocess(
+      src.data_ptr(), src.numel(), src.dtype() == torch::kFloat32,
+      idesc.data_ptr<long>(), fdesc.data_ptr<float>(),
+      work_off.data_ptr<long>(), (int)n_img, n_items, out.data_ptr(),
+      out.numel(), out.dtype() == torch::kFloat32, cur_stream());
+}
+
 // ------------------------------------------------------------------ ranking
 // Shared checks of the per-fit group table (rank_kernels.hip): offsets
 // (G+1) int64, gid (n) int32.  Their contents are validated on the host when
@@ -928,6 +972,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wave-cooperative CSR histogram + in-kernel leaf totals");
   m.def("jpeg_reconstruct", &jpeg_reconstruct,
         "batched JPEG dequant + IDCT + colour conversion into a uint8 buffer");
+  m.def("image_preprocess", &image_preprocess,
+        "fused crop/flip/resize/colour/threshold/normalize of a ragged batch");
+  m.def("image_work_items", &image_work_items,
+        "work items (64 x 8 output tiles) image_preprocess_k spends on Ho x Wo");
   m.def("group_rank", &group_rank,
         "stable descending in-group ranks + per-document rank records");
   m.def("lambdarank_grad", &lambdarank_grad,

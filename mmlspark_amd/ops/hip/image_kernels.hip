@@ -227,3 +227,228 @@ extern "C" void launch_jpeg_reconstruct(
                      stream, coef, qt, img_desc, comp_desc, work_off, n_img,
                      basis, out);
 }
+
+// ---------------------------------------------------------------------------
+// image_preprocess_k: crop / flip / bilinear resize / channel map / threshold /
+// normalize / layout of a batch of images of any mix of sizes, in ONE launch.
+// The contract (plan, arithmetic, limits) is in docs/kernels.md; the numpy
+// reference is ops/cpu_ref.py::image_preprocess and gives the same bits.
+//
+// idesc: (n_img, 24) int64
+//    0 src_off (elements)   1 Hs   2 Ws   3 Cs
+//    4 pre_y0   5 pre_x0    6 Hc   7 Wc        pre-window of the source
+//    8 flags: 1 pre flip x, 2 pre flip y, 4 post flip x, 8 post flip y,
+//             16 resize (else copy path), 32 CHW output (else HWC)
+//    9 Hr  10 Wr                                size after the resize
+//   11 post_y0  12 post_x0  13 Ho  14 Wo       post-window of the resized
+//   15 Co
+//   16 channel map, one byte per output channel: 0..3 source channel, 4 gray
+//   17 gray operands, one byte each: c0, c1, c2 (source channels)
+//   18 out_off (elements)
+//   19 n_ops   20 op kinds, one byte each (IMG_OP_*)
+//   21..23 zero
+// fdesc: (n_img, 34) float32
+//    0 scale_y = (float)Hc / (float)Hr    1 scale_x = (float)Wc / (float)Wr
+//    2 + 8 j ..: op j's operands: threshold {thr, maxVal, -}, normalize
+//                {mean[0..3], std[0..3]}
+// work_off: (n_img + 1) int64 prefix sum of image_work_items(Ho, Wo)
+//
+// A work item is a tile of 64 x 8 output pixels; the 256 threads are 64
+// pixels wide x 4 rows, x fastest, and take two rows each.  Taps are read
+// straight from the flat source (they are L2 hits: neighbouring pixels share
+// them).  ops/backend.py::check_image_descriptors validates the descriptors
+// before every launch; every index built from them is range-checked again
+// here, so a bad descriptor reads zeros and writes nothing.
+constexpr int IMG_TILE_W = 64;
+constexpr int IMG_TILE_H = 8;
+constexpr int IMG_DESC_I = 24;
+constexpr int IMG_DESC_F = 34;
+
+enum {
+  IMG_OP_BINARY = 0,
+  IMG_OP_BINARY_INV = 1,
+  IMG_OP_TRUNC = 2,
+  IMG_OP_TOZERO = 3,
+  IMG_OP_TOZERO_INV = 4,
+  IMG_OP_NORMALIZE = 5,
+};
+
+namespace {
+
+struct ImgAxis {
+  int i0, i1;
+  float l0, l1;
+};
+
+// destination index d of an axis resized n_in -> n_out (scale = n_in / n_out)
+__device__ inline ImgAxis img_axis(int d, float scale, int n_in) {
+  float src = scale * ((float)d + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  ImgAxis a;
+  a.i0 = max(0, min((int)floorf(src), n_in - 1));
+  a.i1 = min(a.i0 + 1, n_in - 1);
+  a.l1 = src - (float)a.i0;
+  a.l0 = 1.0f - a.l1;
+  return a;
+}
+
+__device__ inline float img_pick(const float (&s)[4], int c) {
+  return c == 0 ? s[0] : (c == 1 ? s[1] : (c == 2 ? s[2] : s[3]));
+}
+
+__device__ inline void img_store(unsigned char* p, float v) {
+  p[0] = (unsigned char)fminf(fmaxf(v, 0.f), 255.f);
+}
+__device__ inline void img_store(float* p, float v) { p[0] = v; }
+
+}  // namespace
+
+template <typename TS, typename TO>
+__global__ __launch_bounds__(256) void image_preprocess_k(
+    const TS* __restrict__ src, long src_numel,
+    const long* __restrict__ idesc, const float* __restrict__ fdesc,
+    const long* __restrict__ work_off, int n_img, TO* __restrict__ out,
+    long out_numel) {
+  // which image owns this tile: last i with work_off[i] <= item
+  const long item = blockIdx.x;
+  int lo = 0, hi = n_img;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (work_off[mid] <= item) lo = mid; else hi = mid;
+  }
+  const int img = lo;
+  if (img < 0 || img >= n_img) return;
+  const long* d = idesc + (long)IMG_DESC_I * img;
+  const float* f = fdesc + (long)IMG_DESC_F * img;
+  const long src_off = d[0];
+  const int Hs = (int)d[1], Ws = (int)d[2], Cs = (int)d[3];
+  const int pre_y0 = (int)d[4], pre_x0 = (int)d[5];
+  const int Hc = (int)d[6], Wc = (int)d[7];
+  const int flags = (int)d[8];
+  const int post_y0 = (int)d[11], post_x0 = (int)d[12];
+  const int Ho = (int)d[13], Wo = (int)d[14], Co = (int)d[15];
+  const unsigned cmap = (unsigned)d[16], gmap = (unsigned)d[17];
+  const long out_off = d[18];
+  const int n_ops = min((int)d[19], 4);
+  const unsigned kinds = (unsigned)d[20];
+  const bool resize = flags & 16, chw = flags & 32;
+
+  const int tiles_x = (Wo + IMG_TILE_W - 1) / IMG_TILE_W;
+  const int local = (int)(item - work_off[img]);
+  const int ox = (local % tiles_x) * IMG_TILE_W + (threadIdx.x & 63);
+  const int oy_base = (local / tiles_x) * IMG_TILE_H + (threadIdx.x >> 6);
+  if (ox >= Wo || Co < 1 || Co > 4 || Cs < 1 || Cs > 4) return;
+
+  // x taps are the same for both rows of this thread
+  const int rx = post_x0 + ((flags & 4) ? Wo - 1 - ox : ox);
+  ImgAxis ax;
+  if (resize) {
+    ax = img_axis(rx, f[1], Wc);
+  } else {
+    ax.i0 = ax.i1 = rx; ax.l0 = 1.f; ax.l1 = 0.f;
+  }
+  const int sx0 = pre_x0 + ((flags & 1) ? Wc - 1 - ax.i0 : ax.i0);
+  const int sx1 = pre_x0 + ((flags & 1) ? Wc - 1 - ax.i1 : ax.i1);
+  const bool okx0 = sx0 >= 0 && sx0 < Ws, okx1 = sx1 >= 0 && sx1 < Ws;
+
+#pragma unroll
+  for (int rr = 0; rr < IMG_TILE_H / 4; ++rr) {
+    const int oy = oy_base + 4 * rr;
+    if (oy >= Ho) break;
+    const int ry = post_y0 + ((flags & 8) ? Ho - 1 - oy : oy);
+    ImgAxis ay;
+    if (resize) {
+      ay = img_axis(ry, f[0], Hc);
+    } else {
+      ay.i0 = ay.i1 = ry; ay.l0 = 1.f; ay.l1 = 0.f;
+    }
+    const int sy0 = pre_y0 + ((flags & 2) ? Hc - 1 - ay.i0 : ay.i0);
+    const int sy1 = pre_y0 + ((flags & 2) ? Hc - 1 - ay.i1 : ay.i1);
+    const bool oky0 = sy0 >= 0 && sy0 < Hs, oky1 = sy1 >= 0 && sy1 < Hs;
+    const long b00 = src_off + ((long)sy0 * Ws + sx0) * Cs;
+    const long b01 = src_off + ((long)sy0 * Ws + sx1) * Cs;
+    const long b10 = src_off + ((long)sy1 * Ws + sx0) * Cs;
+    const long b11 = src_off + ((long)sy1 * Ws + sx1) * Cs;
+    const bool ok00 = oky0 && okx0 && b00 >= 0 && b00 + Cs <= src_numel;
+    const bool ok01 = oky0 && okx1 && b01 >= 0 && b01 + Cs <= src_numel;
+    const bool ok10 = oky1 && okx0 && b10 >= 0 && b10 + Cs <= src_numel;
+    const bool ok11 = oky1 && okx1 && b11 >= 0 && b11 + Cs <= src_numel;
+
+    // every source channel once
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c >= Cs) break;
+      const float p00 = ok00 ? (float)src[b00 + c] : 0.f;
+      if (resize) {
+        const float p01 = ok01 ? (float)src[b01 + c] : 0.f;
+        const float p10 = ok10 ? (float)src[b10 + c] : 0.f;
+        const float p11 = ok11 ? (float)src[b11 + c] : 0.f;
+        const float top = ax.l0 * p00 + ax.l1 * p01;
+        const float bot = ax.l0 * p10 + ax.l1 * p11;
+        s[c] = ay.l0 * top + ay.l1 * bot;
+      } else {
+        s[c] = p00;
+      }
+    }
+    float gray = 0.f;
+    if (((cmap | (cmap >> 8) | (cmap >> 16) | (cmap >> 24)) & 4) != 0) {
+      const float c0 = img_pick(s, gmap & 3);
+      const float c1 = img_pick(s, (gmap >> 8) & 3);
+      const float c2 = img_pick(s, (gmap >> 16) & 3);
+      gray = (0.299f * c2 + 0.587f * c1) + 0.114f * c0;
+    }
+
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k >= Co) break;
+      const int code = (cmap >> (8 * k)) & 0xff;
+      float v = code >= 4 ? gray : img_pick(s, code);
+      for (int j = 0; j < n_ops; ++j) {
+        const int kind = (kinds >> (8 * j)) & 0xff;
+        const float* q = f + 2 + 8 * j;
+        const float thr = q[0], mx = q[1];
+        switch (kind) {
+          case IMG_OP_BINARY: v = v > thr ? mx : 0.f; break;
+          case IMG_OP_BINARY_INV: v = v > thr ? 0.f : mx; break;
+          case IMG_OP_TRUNC: v = fminf(v, thr); break;
+          case IMG_OP_TOZERO: v = v > thr ? v : 0.f; break;
+          case IMG_OP_TOZERO_INV: v = v > thr ? 0.f : v; break;
+          case IMG_OP_NORMALIZE: v = (v / 255.0f - q[k]) / q[4 + k]; break;
+          default: break;
+        }
+      }
+      const long o = chw ? out_off + ((long)k * Ho + oy) * Wo + ox
+                         : out_off + ((long)oy * Wo + ox) * Co + k;
+      if (o >= 0 && o < out_numel) img_store(out + o, v);
+    }
+  }
+}
+
+extern "C" long image_work_items(long Ho, long Wo) {
+  if (Ho <= 0 || Wo <= 0) return 0;
+  return ((Wo + IMG_TILE_W - 1) / IMG_TILE_W) *
+         ((Ho + IMG_TILE_H - 1) / IMG_TILE_H);
+}
+
+// src_f32 / out_f32 select the element types (uint8 otherwise);
+// n_items = work_off[n_img] is the grid size.
+extern "C" void launch_image_preprocess(
+    const void* src, long src_numel, int src_f32, const long* idesc,
+    const float* fdesc, const long* work_off, int n_img, long n_items,
+    void* out, long out_numel, int out_f32, hipStream_t stream) {
+  if (n_img <= 0 || n_items <= 0) return;
+  const dim3 grid((unsigned)n_items), block(256);
+#define IMG_LAUNCH(TS, TO)                                                  \
+  hipLaunchKernelGGL((image_preprocess_k<TS, TO>), grid, block, 0, stream,  \
+                     (const TS*)src, src_numel, idesc, fdesc, work_off,     \
+                     n_img, (TO*)out, out_numel)
+  if (src_f32) {
+    if (out_f32) IMG_LAUNCH(float, float);
+    else IMG_LAUNCH(float, unsigned char);
+  } else {
+    if (out_f32) IMG_LAUNCH(unsigned char, float);
+    else IMG_LAUNCH(unsigned char, unsigned char);
+  }
+#undef IMG_LAUNCH
+}
