@@ -715,7 +715,7 @@ ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = N
   stage
 }
 
-ml_image_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, superpixelCol = NULL) {
+ml_image_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, superpixelCol = NULL) {
   stage <- mmlspark_amd$explainers$lime$ImageLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -725,6 +725,7 @@ ml_image_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, 
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
@@ -742,7 +743,7 @@ ml_image_reader <- function(bytesCol = NULL, imageCol = NULL, dropInvalid = NULL
   stage
 }
 
-ml_image_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, superpixelCol = NULL) {
+ml_image_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, superpixelCol = NULL) {
   stage <- mmlspark_amd$explainers$shap$ImageSHAP()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -752,6 +753,7 @@ ml_image_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, 
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(cellSize)) stage$set("cellSize", cellSize)
   if (!is.null(modifier)) stage$set("modifier", modifier)
@@ -1591,7 +1593,7 @@ ml_summarize_data <- function(counts = NULL, basic = NULL, percentiles = NULL) {
   stage
 }
 
-ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL) {
+ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL) {
   stage <- mmlspark_amd$explainers$lime$SuperpixelTransformer()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1601,6 +1603,7 @@ ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClas
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
@@ -1609,7 +1612,7 @@ ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClas
   stage
 }
 
-ml_tabular_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, kernelWidth = NULL, regularization = NULL, inputCols = NULL, backgroundData = NULL) {
+ml_tabular_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCols = NULL, backgroundData = NULL) {
   stage <- mmlspark_amd$explainers$lime$TabularLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1619,6 +1622,7 @@ ml_tabular_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
   if (!is.null(inputCols)) stage$set("inputCols", inputCols)
@@ -1626,7 +1630,7 @@ ml_tabular_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL
   stage
 }
 
-ml_tabular_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, inputCols = NULL, backgroundData = NULL) {
+ml_tabular_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, inputCols = NULL, backgroundData = NULL) {
   stage <- mmlspark_amd$explainers$shap$TabularSHAP()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1636,6 +1640,7 @@ ml_tabular_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(inputCols)) stage$set("inputCols", inputCols)
   if (!is.null(backgroundData)) stage$set("backgroundData", backgroundData)
   stage
@@ -1694,7 +1699,7 @@ ml_text_featurizer_model <- function(inputCol = NULL, outputCol = NULL, useToken
   stage
 }
 
-ml_text_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, tokensCol = NULL) {
+ml_text_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, tokensCol = NULL) {
   stage <- mmlspark_amd$explainers$lime$TextLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1704,6 +1709,7 @@ ml_text_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, o
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
@@ -1720,7 +1726,7 @@ ml_text_preprocessor <- function(inputCol = NULL, outputCol = NULL, normFunc = N
   stage
 }
 
-ml_text_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, inputCol = NULL, tokensCol = NULL) {
+ml_text_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, inputCol = NULL, tokensCol = NULL) {
   stage <- mmlspark_amd$explainers$shap$TextSHAP()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1730,6 +1736,7 @@ ml_text_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, o
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(tokensCol)) stage$set("tokensCol", tokensCol)
   stage
@@ -1926,7 +1933,7 @@ ml_value_indexer_model <- function(inputCol = NULL, outputCol = NULL, levels = N
   stage
 }
 
-ml_vector_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, kernelWidth = NULL, regularization = NULL, featuresCol = NULL, backgroundData = NULL) {
+ml_vector_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, featuresCol = NULL, backgroundData = NULL) {
   stage <- mmlspark_amd$explainers$lime$VectorLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1936,6 +1943,7 @@ ml_vector_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL,
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
@@ -1943,7 +1951,7 @@ ml_vector_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL,
   stage
 }
 
-ml_vector_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, featuresCol = NULL, backgroundData = NULL) {
+ml_vector_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, featuresCol = NULL, backgroundData = NULL) {
   stage <- mmlspark_amd$explainers$shap$VectorSHAP()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1953,6 +1961,7 @@ ml_vector_shap <- function(model = NULL, targetCol = NULL, targetClasses = NULL,
   if (!is.null(metricsCol)) stage$set("metricsCol", metricsCol)
   if (!is.null(seed)) stage$set("seed", seed)
   if (!is.null(rowBatch)) stage$set("rowBatch", rowBatch)
+  if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
   if (!is.null(backgroundData)) stage$set("backgroundData", backgroundData)
   stage

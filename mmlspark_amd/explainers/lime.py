@@ -4,7 +4,10 @@ TextLIME + the legacy Superpixel transformer of core/.../lime/).
 Per row: Bernoulli on/off states → perturbed samples → batched scoring →
 kernel-weighted lasso per target class (kernel weight
 sqrt(exp(-(d/width)^2)), LIMEBase.scala:55-65; per-row lasso :96-113).
-Output per row: (n_classes, m) coefficient matrix."""
+Output per row: (n_classes, m) coefficient matrix.
+With fusedSampling=True, TabularLIME and VectorLIME send each chunk's states
+and drawn background rows to the model's score_coalitions (GBDT models: one
+fused forest kernel, no perturbed samples) and fit the lasso on its output."""
 from __future__ import annotations
 
 import numpy as np
@@ -53,6 +56,25 @@ class LIMEBase(LocalExplainer):
             r2_out.append(np.asarray(r2s))
         return np.stack(coefs)  # (n_classes, m)
 
+    def _fused_chunk_scores(self, model, bg_dev, chunk, bg, states_l, rng,
+                            score_samples):
+        """Scores of the chunk's samples, (len(chunk) * n_samp, C), from the
+        model's fused coalition kernel.  rng is consumed as the sample path
+        does: the states are drawn already, now one draw of background rows
+        per explained row.  bg_dev is the model's device copy of bg, made
+        once per transform.  If the model declines, the same draws feed
+        score_samples."""
+        n = states_l[0].shape[0]
+        draws = [self._draw_background(rng, len(bg), n, 1) for _ in chunk]
+        v = model.score_coalitions(
+            chunk, bg_dev, np.stack(states_l), np.stack(draws), 1,
+            self.get("targetCol"), self.get("targetClasses"))
+        if v is not None:
+            return v
+        return score_samples(np.concatenate(
+            [st * x[None, :] + (1 - st) * bg[d]
+             for x, st, d in zip(chunk, states_l, draws)]))
+
 
 @register
 class TabularLIME(LIMEBase):
@@ -70,13 +92,20 @@ class TabularLIME(LIMEBase):
         r2s = []
         rows = df[cols].to_numpy(dtype=np.float64)
         batch = self.get("rowBatch")
+        fused, bg_dev = self._fused_model(bg)
         for s0 in range(0, len(rows), batch):
             chunk = rows[s0:s0 + batch]
             states_l = [lime_sample_states(m, n_samp, rng) for _ in chunk]
-            perts = [VectorSampler(bg, rng).apply(x, st)
-                     for x, st in zip(chunk, states_l)]
-            # one scoring fan-out for the whole chunk
-            scores = self._score_matrix(np.concatenate(perts), cols)                 if perts else np.zeros((0, 1))
+            if fused is not None:
+                scores = self._fused_chunk_scores(
+                    fused, bg_dev, chunk, bg, states_l, rng,
+                    lambda p: self._score_matrix(p, cols))
+                perts = states_l   # one score per state, as one per sample
+            else:
+                perts = [VectorSampler(bg, rng).apply(x, st)
+                         for x, st in zip(chunk, states_l)]
+                # one scoring fan-out for the whole chunk
+                scores = self._score_matrix(np.concatenate(perts), cols)                 if perts else np.zeros((0, 1))
             o = 0
             for st, p_ in zip(states_l, perts):
                 explanations.append(
@@ -107,12 +136,19 @@ class VectorLIME(LIMEBase):
         explanations = []
         r2s = []
         batch = self.get("rowBatch")
+        fused, bg_dev = self._fused_model(bg)
         for s0 in range(0, len(rows), batch):
             chunk = rows[s0:s0 + batch]
             states_l = [lime_sample_states(m, n_samp, rng) for _ in chunk]
-            perts = [VectorSampler(bg, rng).apply(x, st).astype(np.float32)
-                     for x, st in zip(chunk, states_l)]
-            scores = self._score_matrix(np.concatenate(perts))                 if perts else np.zeros((0, 1))
+            if fused is not None:
+                scores = self._fused_chunk_scores(
+                    fused, bg_dev, chunk, bg, states_l, rng,
+                    lambda p: self._score_matrix(p.astype(np.float32)))
+                perts = states_l   # one score per state, as one per sample
+            else:
+                perts = [VectorSampler(bg, rng).apply(x, st).astype(np.float32)
+                         for x, st in zip(chunk, states_l)]
+                scores = self._score_matrix(np.concatenate(perts))                 if perts else np.zeros((0, 1))
             o = 0
             for st, p_ in zip(states_l, perts):
                 explanations.append(

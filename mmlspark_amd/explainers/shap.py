@@ -10,6 +10,11 @@ KernelSHAPBase.scala:69-93 — leftover sample budget becomes background
 draws, cycling the full background exactly when it fits), then solve the
 constrained weighted least squares for every row and class at once (the
 coalition design is shared, so one factorization serves the whole chunk).
+With fusedSampling=True, TabularSHAP and VectorSHAP hand the coalitions, the
+background and the drawn background rows to the model's score_coalitions
+(GBDT models: one fused forest kernel per chunk, the perturbed samples never
+built); only the background and the explained rows themselves are still
+scored through score_matrix.
 Output per row: (n_classes, m+1) — [base_value, phi_1..phi_m] per class."""
 from __future__ import annotations
 
@@ -40,9 +45,38 @@ def _mean_over_draws(scores, n_rows, nZ, B):
     return np.concatenate([head, tail])
 
 
+def _perturb(x, states, bg, draw):
+    """VectorSampler.apply with the background rows already chosen: `draw`
+    holds one row index per state, None cycles the background."""
+    if draw is None:
+        draw = np.tile(np.arange(len(bg)), len(states) // len(bg))
+    return states * x[None, :] + (1 - states) * bg[draw]
+
+
 class KernelSHAPBase(LocalExplainer):
     def _default_samples(self, m):
         return 2 * m + 2048
+
+    def _fused_chunk_scores(self, model, bg_dev, chunk, bg, Z, B, rng,
+                            score_rest):
+        """The chunk's scores in _mean_over_draws' layout from the model's
+        fused coalition kernel: rng is consumed as VectorSampler would, one
+        draw of nZ*B background rows per explained row unless the background
+        is cycled.  bg_dev is the model's device copy of bg, made once per
+        transform.  score_rest scores the background and the rows themselves.  If the model declines, the same draws feed the sample
+        path, so the explanation does not depend on who scored it."""
+        nZ = Z.shape[0]
+        draws = [self._draw_background(rng, len(bg), nZ * B, B)
+                 for _ in chunk]
+        head = model.score_coalitions(
+            chunk, bg_dev, Z, None if draws[0] is None else np.stack(draws), B,
+            self.get("targetCol"), self.get("targetClasses"))
+        if head is not None:
+            return np.concatenate([head, score_rest(None)])
+        Zrep = np.repeat(Z, B, axis=0)
+        pert = np.concatenate([_perturb(x, Zrep, bg, d)
+                               for x, d in zip(chunk, draws)])
+        return _mean_over_draws(score_rest(pert), len(chunk), nZ, B)
 
     def _solve_batch(self, Z, scores, nZ, n_pert, n_bg, w, v_null,
                      n_rows):
@@ -98,19 +132,28 @@ class TabularSHAP(KernelSHAPBase):
         Zrep = np.repeat(Z, B, axis=0)
         explanations = []
         batch = self.get("rowBatch")
+        fused, bg_dev = self._fused_model(bg)
         rows = df[cols].to_numpy(dtype=np.float64)
         for s in range(0, len(rows), batch):
             chunk = rows[s:s + batch]
-            frames = []
-            for x in chunk:
-                sampler = VectorSampler(bg, rng)
-                pert = sampler.apply(x, Zrep, draws_per_state=B)
-                frames.append(pert)
-            all_pert = np.concatenate(frames) if frames else np.zeros((0, m))
-            # v_null from background mean prediction, v_full from the row
-            raw_scores = self._score_matrix(
-                np.concatenate([all_pert, bg, chunk]), cols)
-            scores = _mean_over_draws(raw_scores, len(chunk), nZ, B)
+            if fused is not None:
+                scores = self._fused_chunk_scores(
+                    fused, bg_dev, chunk, bg, Z, B, rng,
+                    lambda pert: self._score_matrix(np.concatenate(
+                        [bg, chunk] if pert is None else [pert, bg, chunk]),
+                        cols))
+            else:
+                frames = []
+                for x in chunk:
+                    sampler = VectorSampler(bg, rng)
+                    pert = sampler.apply(x, Zrep, draws_per_state=B)
+                    frames.append(pert)
+                all_pert = np.concatenate(frames) if frames \
+                    else np.zeros((0, m))
+                # v_null from background mean prediction, v_full from the row
+                raw_scores = self._score_matrix(
+                    np.concatenate([all_pert, bg, chunk]), cols)
+                scores = _mean_over_draws(raw_scores, len(chunk), nZ, B)
             v_null = scores[len(chunk) * nZ:
                             len(chunk) * nZ + len(bg)].mean(axis=0)
             explanations.extend(self._solve_batch(
@@ -141,16 +184,23 @@ class VectorSHAP(KernelSHAPBase):
         rows = vector_column_to_matrix(df, fcol).astype(np.float64)
         explanations = []
         batch = self.get("rowBatch")
+        fused, bg_dev = self._fused_model(bg)
         for s in range(0, len(rows), batch):
             chunk = rows[s:s + batch]
-            pert_frames = [VectorSampler(bg, rng).apply(x, Zrep,
-                                                        draws_per_state=B)
-                           for x in chunk]
-            all_pert = np.concatenate(pert_frames)
-            full = np.concatenate([bg, chunk])
-            raw_scores = self._score_matrix(
-                np.concatenate([all_pert, full]).astype(np.float32))
-            scores = _mean_over_draws(raw_scores, len(chunk), nZ, B)
+            if fused is not None:
+                scores = self._fused_chunk_scores(
+                    fused, bg_dev, chunk, bg, Z, B, rng,
+                    lambda pert: self._score_matrix(np.concatenate(
+                        [bg, chunk] if pert is None else [pert, bg, chunk]
+                    ).astype(np.float32)))
+            else:
+                pert_frames = [VectorSampler(bg, rng).apply(
+                    x, Zrep, draws_per_state=B) for x in chunk]
+                all_pert = np.concatenate(pert_frames)
+                full = np.concatenate([bg, chunk])
+                raw_scores = self._score_matrix(
+                    np.concatenate([all_pert, full]).astype(np.float32))
+                scores = _mean_over_draws(raw_scores, len(chunk), nZ, B)
             v_null = scores[len(chunk) * nZ:
                             len(chunk) * nZ + len(bg)].mean(axis=0)
             explanations.extend(self._solve_batch(

@@ -417,6 +417,92 @@ class _GBDTModelBase(Model):
             return v
         return v[:, list(classes)]
 
+    def coalition_background(self, bg: np.ndarray) -> torch.Tensor:
+        """The background table as score_coalitions takes it: float32 on the
+        model's device.  An explainer calls this once per transform."""
+        return torch.from_numpy(np.ascontiguousarray(
+            bg, dtype=np.float32)).to(default_device(self.get("device")))
+
+    def score_coalitions(self, X: np.ndarray, bg: torch.Tensor,
+                         states: np.ndarray, bidx, B: int, target_col: str,
+                         classes):
+        """Explainer fused path (LocalExplainer fusedSampling): the values
+        score_matrix would give for the perturbed samples
+        states * x + (1 - states) * bg[bidx], already averaged over the B
+        draws of each coalition, without building a sample —
+        backend.coalition_values selects each feature value inside the
+        forest walk.
+
+        X (R, m) explained rows; bg (nb, m) background from
+        coalition_background, shared by every chunk; states (nZ, m)
+        shared by the rows or (R, nZ, m) per row, 0/1; bidx (R, nZ * B)
+        background row per draw, or None to cycle the whole background
+        (B == nb).  Returns (R * nZ, C) float64, row-major over (row,
+        coalition), C as score_matrix has it — or None when the explainer
+        must score the samples itself: a thresholded or argmax
+        predictionCol, an unknown target column, or a model beyond
+        EXPLAIN_MAX_FEATURES / EXPLAIN_MAX_OUTPUTS."""
+        from ...ops import backend
+        b = self.booster
+        K, m = b.n_outputs, X.shape[1]
+        if (not b.trees or m != b.n_features or bg.shape[1] != m
+                or m > backend.EXPLAIN_MAX_FEATURES
+                or K > backend.EXPLAIN_MAX_OUTPUTS or len(X) > 65535):
+            return None
+        params = self.params()
+        prob_col = self.get("probabilityCol") if "probabilityCol" in params \
+            else None
+        raw_col = self.get("rawPredictionCol") if "rawPredictionCol" in params \
+            else None
+        binary = b.objective == "binary"
+        multi = b.objective in ("multiclass", "softmax")
+        classes = [int(c) for c in classes]
+        flip = False
+        if target_col == prob_col:
+            transform = "sigmoid" if binary else \
+                "softmax" if multi else "identity"
+        elif target_col == raw_col:
+            transform, flip = "identity", binary
+        elif target_col == self.get("predictionCol") and not (binary or multi):
+            transform = "identity"
+        else:
+            return None
+        if transform == "sigmoid" and K != 1 or transform == "softmax" and K < 2:
+            return None
+        n_cols = 2 if transform == "sigmoid" else K
+        picked = [0] if (n_cols == 1 or flip) else classes
+        device = bg.device
+        states = np.asarray(states)
+        if states.ndim == 2:
+            states = states[None]
+        nZ, W = states.shape[1], (m + 31) // 32
+        packed = np.zeros(states.shape[:2] + (W * 4,), dtype=np.uint8)
+        bits = np.packbits(states > 0.5, axis=-1, bitorder="little")
+        packed[..., :bits.shape[-1]] = bits
+        masks = torch.from_numpy(packed.view("<i4")).to(device)
+        if bidx is not None:
+            bidx = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(bidx).reshape(len(X), nZ, B), dtype=np.int32))
+        num_it = self.get("numIterations")
+        if num_it < 0 and getattr(b, "best_iteration", -1) >= 0:
+            num_it = b.best_iteration + 1
+        f = b._flat(device)
+        v = backend.coalition_values(
+            f["feature"], f["threshold"], f["left"], f["right"], f["value"],
+            f["offsets"], f["weights"],
+            torch.from_numpy(np.ascontiguousarray(
+                X, dtype=np.float32)).to(device),
+            bg, masks, bidx, B,
+            torch.from_numpy(np.resize(b.base_score, K).astype(np.float32)
+                             ).to(device),
+            K, transform, float(b.sigmoid), picked,
+            start_tree=self.get("startIteration") * K, num_iteration=num_it,
+            cat_offset=f.get("cat_offset"), cat_words=f.get("cat_words"))
+        v = v.reshape(len(X) * nZ, len(picked)).cpu().numpy()
+        if flip:  # [-raw, raw]: linear, so it commutes with the mean
+            v = np.concatenate([-v, v], axis=1)[:, classes]
+        return v
+
     def _X(self, df: pd.DataFrame, device):
         from .sparse import CsrMatrix, looks_sparse
         fc = self.get("featuresCol")

@@ -381,6 +381,157 @@ def knn_topk(Q, X, xsq, k, label_ids=None, allow_bits=None, splits=0):
                             int(splits))
 
 
+# --------------------------------------------------------------- explainers
+EXPLAIN_MAX_FEATURES = 256    # coalition_values_k keeps 8 mask words per item
+EXPLAIN_MAX_OUTPUTS = 8       # raw sums per item held in registers
+EXPLAIN_MAX_TILE_NODES = 6144  # packed nodes of one forest tile in LDS
+EXPLAIN_TRANSFORMS = {"identity": 0, "sigmoid": 1, "softmax": 2}
+
+
+def check_coalition_inputs(forest, X, bg, masks, bidx, B, base, n_outputs,
+                           transform, classes, start_tree, end_tree,
+                           tile_nodes):
+    """Everything coalition_values indexes with, checked in O(inputs);
+    raises ValueError and nothing is launched."""
+    def bad(msg):
+        raise ValueError("coalition_values: " + msg)
+
+    feat, thr, left, right, val, offsets, weights, cat_off, cat_words = forest
+    named = [("feature", feat, torch.int32, 1), ("left", left, torch.int32, 1),
+             ("right", right, torch.int32, 1),
+             ("threshold", thr, torch.float32, 1),
+             ("value", val, torch.float32, 1),
+             ("offsets", offsets, torch.int64, 1),
+             ("weights", weights, torch.float32, 1),
+             ("X", X, torch.float32, 2), ("bg", bg, torch.float32, 2),
+             ("masks", masks, torch.int32, 3),
+             ("base", base, torch.float32, 1)]
+    if cat_off is not None and cat_words is not None:
+        named += [("cat_offset", cat_off, torch.int32, 1),
+                  ("cat_words", cat_words, torch.int32, 1)]
+    for name, t, dtype, dim in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            bad("%s must be a %s tensor" % (name, dtype))
+        if t.dim() != dim:
+            bad("%s must have %d dimension(s)" % (name, dim))
+        if not t.is_contiguous():
+            bad(name + " must be contiguous")
+        if t.device != X.device:
+            bad(name + " must live where X lives")
+    n_nodes, T = feat.numel(), offsets.numel() - 1
+    if any(t.numel() != n_nodes for t in (thr, left, right, val)):
+        bad("the node arrays must have one length")
+    if T < 0 or weights.numel() != T:
+        bad("weights must hold one weight per tree")
+    if not 0 <= start_tree <= end_tree <= T:
+        bad("the tree range must satisfy 0 <= t0 <= t1 <= T")
+    if not 1 <= n_outputs <= EXPLAIN_MAX_OUTPUTS:
+        bad("n_outputs must be in [1, %d]" % EXPLAIN_MAX_OUTPUTS)
+    if base.numel() != n_outputs:
+        bad("base must hold one value per output")
+    R, nf = X.shape
+    nb = bg.shape[0]
+    if not 1 <= nf <= EXPLAIN_MAX_FEATURES:
+        bad("the feature count must be in [1, %d]" % EXPLAIN_MAX_FEATURES)
+    if bg.shape[1] != nf or nb < 1:
+        bad("bg must be (nb >= 1, nf)")
+    if R > 65535:
+        bad("at most 65535 rows per call")
+    Rm, nZ, W = masks.shape
+    if W != (nf + 31) // 32:
+        bad("masks must have ceil(nf / 32) words per coalition")
+    if Rm != 1 and Rm != R:
+        bad("masks must have 1 row (shared) or one per explained row")
+    if int(B) < 1:
+        bad("B must be at least 1")
+    if bidx is None:
+        if int(B) != nb:
+            bad("without bidx the background is cycled, which needs B == nb")
+    else:
+        if bidx.dtype != torch.int32 or tuple(bidx.shape) != (R, nZ, int(B)):
+            bad("bidx must be (R, nZ, B) int32")
+        if bidx.numel() and (int(bidx.min()) < 0 or int(bidx.max()) >= nb):
+            bad("bidx must lie in [0, nb)")
+    if transform not in EXPLAIN_TRANSFORMS:
+        bad("transform must be one of %s" % sorted(EXPLAIN_TRANSFORMS))
+    if transform == "sigmoid" and n_outputs != 1:
+        bad("the binary sigmoid needs n_outputs == 1")
+    if transform == "softmax" and n_outputs < 2:
+        bad("softmax needs n_outputs >= 2")
+    n_classes = 2 if transform == "sigmoid" else n_outputs
+    if any(not 0 <= int(c) < n_classes for c in classes):
+        bad("every class must be in [0, %d)" % n_classes)
+    if not 0 <= int(tile_nodes) <= EXPLAIN_MAX_TILE_NODES:
+        bad("tile_nodes must be in [0, %d] (0 = automatic)"
+            % EXPLAIN_MAX_TILE_NODES)
+
+
+def coalition_values(node_feature, node_threshold, node_left, node_right,
+                     node_value, tree_offsets, tree_weights, X, bg, masks,
+                     bidx, B, base, n_outputs, transform="identity",
+                     sigmoid=1.0, classes=(0,), start_tree=0,
+                     num_iteration=-1, cat_offset=None, cat_words=None,
+                     tile_nodes=0):
+    """KernelSHAP / LIME coalition values of a GBDT forest without building
+    the perturbed samples: for every explained row r and coalition z the mean
+    over B background draws of the transformed model output, where feature j
+    of a sample is X[r, j] if bit j of the coalition is set and the drawn
+    background row's value otherwise.
+
+    The forest is Booster._flat's arrays; trees [start_tree, end) are used,
+    end following predict_forest's num_iteration rule.  X (R, nf) and bg
+    (nb, nf) float32.  masks (Rm, nZ, W) int32 with W = ceil(nf / 32), bit j
+    of a coalition in word j >> 5 at position j & 31 (words read as
+    unsigned); Rm is 1 for coalitions shared by all rows or R.  bidx
+    (R, nZ, B) int32 names the background row of each draw and may still be
+    on the host (it is range-checked, then moved to X's device); None cycles
+    the background, draw d using row d, and needs B == nb.  base (n_outputs)
+    float32 is added to the raw sums.  transform: "identity"; "sigmoid",
+    n_outputs == 1, class 1 = 1 / (1 + exp(-sigmoid * raw)) and class 0 its
+    complement; or "softmax" over the n_outputs raw sums.  classes picks the
+    output columns.  tile_nodes > 0 fixes how many nodes the device stages
+    per forest tile; the result does not depend on it up to float32 sum
+    order, and not at all when the leaves sum exactly.
+
+    Raw sums are float32 on the device (base first, then the trees in order
+    by fused multiply-add), the transform and the mean float64.  Returns
+    (R, nZ, len(classes)) float64 on X's device, bit-repeatable."""
+    n_trees = tree_offsets.numel() - 1
+    end_tree = n_trees if num_iteration < 0 else min(
+        n_trees, start_tree + num_iteration * n_outputs)
+    end_tree = max(end_tree, start_tree)
+    if bidx is not None:
+        bidx = torch.as_tensor(bidx)
+    check_coalition_inputs(
+        (node_feature, node_threshold, node_left, node_right, node_value,
+         tree_offsets, tree_weights, cat_offset, cat_words), X, bg, masks,
+        bidx, B, base, n_outputs, transform, classes, start_tree, end_tree,
+        tile_nodes)
+    if bidx is not None:
+        bidx = bidx.to(X.device).contiguous()
+    classes = [int(c) for c in classes]
+    if X.is_cuda:
+        ext = _require_ext()
+        if (ext.EXPLAIN_MAX_FEATURES, ext.EXPLAIN_MAX_OUTPUTS,
+                ext.EXPLAIN_MAX_TILE_NODES) != (
+                EXPLAIN_MAX_FEATURES, EXPLAIN_MAX_OUTPUTS,
+                EXPLAIN_MAX_TILE_NODES):
+            raise RuntimeError("coalition_values: the built extension has "
+                               "other limits than ops/backend.py; rebuild it")
+        return ext.coalition_values(
+            node_feature, node_threshold, node_left, node_right, node_value,
+            tree_offsets, tree_weights, cat_offset, cat_words, int(n_outputs),
+            int(start_tree), int(end_tree), X, bg, masks, bidx, int(B), base,
+            EXPLAIN_TRANSFORMS[transform], float(sigmoid),
+            torch.tensor(classes, dtype=torch.int32, device=X.device),
+            int(tile_nodes))
+    return cpu_ref.coalition_values(
+        node_feature, node_threshold, node_left, node_right, node_value,
+        tree_offsets, tree_weights, X, bg, masks, bidx, int(B), base,
+        int(n_outputs), transform, float(sigmoid), classes, int(start_tree),
+        int(end_tree), cat_offset, cat_words, int(tile_nodes))
+
+
 # ------------------------------------------------------------ recommendation
 SAR_MAX_K = 128        # sar_recommend_topk_k keeps 2k (score, item) pairs in LDS
 SAR_MAX_TILE = 16384   # LDS cells of one item tile

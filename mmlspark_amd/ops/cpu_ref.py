@@ -884,3 +884,57 @@ def sar_score_pairs(a_indptr, a_col, a_val, s_indptr, s_col, s_val, users,
         part.index_add_(0, own[hit], a_val[e][hit] * s_val[pos[hit]])
         out[sel] = part
     return out
+
+
+# ------------------------------------------------------------- explainers
+def coalition_values(node_feature, node_threshold, node_left, node_right,
+                     node_value, tree_offsets, tree_weights, X, bg, masks,
+                     bidx, B, base, n_outputs, transform, sigmoid, classes,
+                     start_tree, end_tree, cat_offset=None, cat_words=None,
+                     tile_nodes=0, chunk_rows=1 << 16):
+    """backend.coalition_values on the CPU: the perturbed samples are built
+    by float32 select, `chunk_rows` at a time, walked with _traverse, and
+    everything after the leaves (weighted sum, base, transform, mean over
+    the draws) is float64.  tile_nodes is a device matter and is ignored."""
+    R, nf = X.shape
+    nb = bg.shape[0]
+    Rm, nZ, _ = masks.shape
+    C = len(classes)
+    out = torch.zeros(R, nZ, C, dtype=torch.float64)
+    if R == 0 or nZ == 0 or C == 0:
+        return out
+    bits = ((masks.long().unsqueeze(-1) >> torch.arange(32)) & 1).bool()
+    bits = bits.reshape(Rm, nZ, -1)[:, :, :nf]              # (Rm, nZ, nf)
+    T = end_tree - start_tree
+    bases = tree_offsets[start_tree:end_tree].long()
+    w = tree_weights[start_tree:end_tree].double()
+    cls = torch.arange(start_tree, end_tree) % n_outputs
+    per_z = max(1, chunk_rows // B)
+    for r in range(R):
+        on_r = bits[0 if Rm == 1 else r]
+        for z0 in range(0, nZ, per_z):
+            z1 = min(nZ, z0 + per_z)
+            if bidx is None:
+                rows = torch.arange(B).expand(z1 - z0, B)
+            else:
+                rows = bidx[r, z0:z1].long()
+            on = on_r[z0:z1].unsqueeze(1)                   # (z, 1, nf)
+            S = torch.where(on, X[r].view(1, 1, nf), bg[rows])
+            S = S.reshape(-1, nf)
+            raw = base.double().repeat(S.shape[0], 1)       # (z*B, K)
+            if T > 0:
+                leaf = _traverse(node_feature, node_threshold, node_left,
+                                 node_right, bases, S.shape[0],
+                                 lambda rr, f: S[rr, f], cat_offset,
+                                 cat_words)
+                raw.index_add_(1, cls, node_value[leaf].double() * w)
+            if transform == "sigmoid":
+                p = 1.0 / (1.0 + torch.exp(-float(sigmoid) * raw))
+                vals = torch.cat([1.0 - p, p], dim=1)
+            elif transform == "softmax":
+                vals = torch.softmax(raw, dim=1)
+            else:
+                vals = raw
+            vals = vals[:, list(classes)].reshape(z1 - z0, B, C)
+            out[r, z0:z1] = vals.sum(dim=1) / float(B)
+    return out

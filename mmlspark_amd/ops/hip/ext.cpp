@@ -99,6 +99,14 @@ int launch_sar_recommend(const long*, const int*, const float*, const long*,
 int launch_sar_score_pairs(const long*, const int*, const float*, const long*,
                            const int*, const float*, const int*, const int*,
                            long, int, int, float*, hipStream_t);
+int explain_draw_splits(long, long, int);
+int launch_coalition_values(const int*, const float*, const int*, const int*,
+                            const float*, const long*, const float*,
+                            const int*, const unsigned*, long, int, int, int,
+                            const float*, long, const float*, int, int,
+                            const unsigned*, int, int, const int*, int,
+                            const float*, int, float, const int*, int, int,
+                            double*, double*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -941,6 +949,125 @@ torch::Tensor sar_score_pairs(
   return out;
 }
 
+// --------------------------------------------------------------- explainers
+// explain_kernels.hip.  The contents of bidx and classes are range-checked by
+// the caller (ops/backend.py); the kernel clamps bidx and node features again,
+// and a class outside the outputs yields 0.
+static const int kExplainMaxFeatures = 256;
+static const int kExplainMaxOutputs = 8;
+static const int kExplainMaxTileNodes = 6144;
+
+static void explain_check(const torch::Tensor& t, const char* name,
+                          torch::ScalarType dtype, int dim,
+                          const torch::Tensor& X) {
+  TORCH_CHECK(t.is_cuda() && t.device() == X.device(), "coalition_values: ",
+              name, " must be on X's GPU");
+  TORCH_CHECK(t.is_contiguous(), "coalition_values: ", name,
+              " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == dtype, "coalition_values: ", name,
+              " must be ", c10::toString(dtype));
+  TORCH_CHECK(t.dim() == dim, "coalition_values: ", name, " must have ", dim,
+              " dimension(s)");
+}
+
+torch::Tensor coalition_values(
+    torch::Tensor feat, torch::Tensor thr, torch::Tensor left,
+    torch::Tensor right, torch::Tensor val, torch::Tensor offsets,
+    torch::Tensor tw, c10::optional<torch::Tensor> cat_offset,
+    c10::optional<torch::Tensor> cat_words, long n_outputs, long t0, long t1,
+    torch::Tensor X, torch::Tensor bg, torch::Tensor masks,
+    c10::optional<torch::Tensor> bidx, long B, torch::Tensor base,
+    long transform, double sigmoid, torch::Tensor classes, long tile_nodes) {
+  explain_check(feat, "feature", torch::kInt32, 1, X);
+  explain_check(thr, "threshold", torch::kFloat32, 1, X);
+  explain_check(left, "left", torch::kInt32, 1, X);
+  explain_check(right, "right", torch::kInt32, 1, X);
+  explain_check(val, "value", torch::kFloat32, 1, X);
+  explain_check(offsets, "offsets", torch::kInt64, 1, X);
+  explain_check(tw, "weights", torch::kFloat32, 1, X);
+  explain_check(X, "X", torch::kFloat32, 2, X);
+  explain_check(bg, "bg", torch::kFloat32, 2, X);
+  explain_check(masks, "masks", torch::kInt32, 3, X);
+  explain_check(base, "base", torch::kFloat32, 1, X);
+  explain_check(classes, "classes", torch::kInt32, 1, X);
+  const long n_nodes = feat.numel();
+  const long T = offsets.numel() - 1;
+  TORCH_CHECK(thr.numel() == n_nodes && left.numel() == n_nodes &&
+              right.numel() == n_nodes && val.numel() == n_nodes,
+              "coalition_values: the node arrays must have one length");
+  TORCH_CHECK(T >= 0 && tw.numel() == T,
+              "coalition_values: weights must hold one weight per tree");
+  TORCH_CHECK(0 <= t0 && t0 <= t1 && t1 <= T,
+              "coalition_values: tree range must satisfy 0 <= t0 <= t1 <= T");
+  TORCH_CHECK(n_outputs >= 1 && n_outputs <= kExplainMaxOutputs,
+              "coalition_values: n_outputs must be in [1, ",
+              kExplainMaxOutputs, "]");
+  TORCH_CHECK(base.numel() == n_outputs,
+              "coalition_values: base must hold one value per output");
+  const long R = X.size(0), nf = X.size(1), nb = bg.size(0);
+  TORCH_CHECK(nf >= 1 && nf <= kExplainMaxFeatures,
+              "coalition_values: feature count must be in [1, ",
+              kExplainMaxFeatures, "]");
+  TORCH_CHECK(bg.size(1) == nf && nb >= 1 && nb < (1L << 31) / nf,
+              "coalition_values: bg must be (nb >= 1, nf)");
+  TORCH_CHECK(R <= 65535, "coalition_values: at most 65535 rows per call");
+  const long Rm = masks.size(0), nZ = masks.size(1), W = masks.size(2);
+  TORCH_CHECK(W == (nf + 31) / 32,
+              "coalition_values: masks must have ceil(nf / 32) words");
+  TORCH_CHECK(Rm == 1 || Rm == R,
+              "coalition_values: masks must have 1 or R rows");
+  TORCH_CHECK(B >= 1 && B < (1L << 24),
+              "coalition_values: B must be at least 1");
+  TORCH_CHECK(nZ < (1L << 31) / B,
+              "coalition_values: too many coalitions x draws");
+  const int* bi = nullptr;
+  if (bidx.has_value()) {
+    explain_check(*bidx, "bidx", torch::kInt32, 3, X);
+    TORCH_CHECK(bidx->size(0) == R && bidx->size(1) == nZ &&
+                bidx->size(2) == B,
+                "coalition_values: bidx must be (R, nZ, B)");
+    bi = bidx->data_ptr<int>();
+  } else {
+    TORCH_CHECK(B == nb, "coalition_values: without bidx the background is "
+                "cycled, which needs B == nb");
+  }
+  TORCH_CHECK(transform >= 0 && transform <= 2,
+              "coalition_values: transform must be 0, 1 or 2");
+  TORCH_CHECK(transform != 1 || n_outputs == 1,
+              "coalition_values: the binary sigmoid needs n_outputs == 1");
+  TORCH_CHECK(transform != 2 || n_outputs >= 2,
+              "coalition_values: softmax needs n_outputs >= 2");
+  const long C = classes.numel();
+  TORCH_CHECK(tile_nodes >= 0 && tile_nodes <= kExplainMaxTileNodes,
+              "coalition_values: tile_nodes must be in [0, ",
+              kExplainMaxTileNodes, "] (0 = automatic)");
+  auto [co, cw] = cat_ptrs(cat_offset, cat_words);
+  if (co != nullptr) {
+    explain_check(*cat_offset, "cat_offset", torch::kInt32, 1, X);
+    explain_check(*cat_words, "cat_words", torch::kInt32, 1, X);
+    TORCH_CHECK(cat_offset->numel() == n_nodes,
+                "coalition_values: cat_offset must hold one entry per node");
+  }
+  auto out = torch::empty({R, nZ, C}, X.options().dtype(torch::kFloat64));
+  if (R == 0 || nZ == 0 || C == 0) return out;
+  const int dsplit = explain_draw_splits(R, nZ, (int)B);
+  auto part = torch::empty({dsplit > 1 ? R * nZ * dsplit * C : 0},
+                           out.options());
+  const int err = launch_coalition_values(
+      feat.data_ptr<int>(), thr.data_ptr<float>(), left.data_ptr<int>(),
+      right.data_ptr<int>(), val.data_ptr<float>(), offsets.data_ptr<long>(),
+      tw.data_ptr<float>(), co, cw, n_nodes, (int)t0, (int)t1, (int)n_outputs,
+      X.data_ptr<float>(), R, bg.data_ptr<float>(), (int)nb, (int)nf,
+      (const unsigned*)masks.data_ptr<int>(), (int)Rm, (int)nZ, bi, (int)B,
+      base.data_ptr<float>(), (int)transform, (float)sigmoid,
+      classes.data_ptr<int>(), (int)C, (int)tile_nodes,
+      part.data_ptr<double>(), out.data_ptr<double>(), cur_stream());
+  TORCH_CHECK(err == 0, "coalition_values launch failed: ",
+              err < 0 ? "argument out of range"
+                      : hipGetErrorString((hipError_t)err));
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -992,6 +1119,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "SAR score of (user, item) pairs, bit-equal to sar_recommend's");
   m.def("sar_default_tile", &sar_default_tile,
         "tile the SAR launchers pick (which: 0 co-occurrence, 1 recommend)");
+  m.def("coalition_values", &coalition_values,
+        "mean transformed forest output per (row, coalition), samples never "
+        "built");
+  m.attr("EXPLAIN_MAX_FEATURES") = kExplainMaxFeatures;
+  m.attr("EXPLAIN_MAX_OUTPUTS") = kExplainMaxOutputs;
+  m.attr("EXPLAIN_MAX_TILE_NODES") = kExplainMaxTileNodes;
   m.attr("SAR_MAX_K") = kSarMaxK;
   m.attr("SAR_MAX_TILE") = kSarMaxTile;
 }
