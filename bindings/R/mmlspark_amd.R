@@ -2,7 +2,7 @@
 library(reticulate)
 mmlspark_amd <- import("mmlspark_amd")
 
-ml_access_anomaly <- function(tenantCol = NULL, indexedUserCol = NULL, indexedResCol = NULL, rankParam = NULL, regParam = NULL, maxIter = NULL, complementsetFactor = NULL, negScore = NULL, outputCol = NULL, seed = NULL) {
+ml_access_anomaly <- function(tenantCol = NULL, indexedUserCol = NULL, indexedResCol = NULL, rankParam = NULL, regParam = NULL, maxIter = NULL, complementsetFactor = NULL, negScore = NULL, outputCol = NULL, seed = NULL, device = NULL, applyImplicitCf = NULL, alphaParam = NULL, likelihoodCol = NULL, lowValue = NULL, highValue = NULL) {
   stage <- mmlspark_amd$models$cyber$AccessAnomaly()
   if (!is.null(tenantCol)) stage$set("tenantCol", tenantCol)
   if (!is.null(indexedUserCol)) stage$set("indexedUserCol", indexedUserCol)
@@ -14,10 +14,16 @@ ml_access_anomaly <- function(tenantCol = NULL, indexedUserCol = NULL, indexedRe
   if (!is.null(negScore)) stage$set("negScore", negScore)
   if (!is.null(outputCol)) stage$set("outputCol", outputCol)
   if (!is.null(seed)) stage$set("seed", seed)
+  if (!is.null(device)) stage$set("device", device)
+  if (!is.null(applyImplicitCf)) stage$set("applyImplicitCf", applyImplicitCf)
+  if (!is.null(alphaParam)) stage$set("alphaParam", alphaParam)
+  if (!is.null(likelihoodCol)) stage$set("likelihoodCol", likelihoodCol)
+  if (!is.null(lowValue)) stage$set("lowValue", lowValue)
+  if (!is.null(highValue)) stage$set("highValue", highValue)
   stage
 }
 
-ml_access_anomaly_model <- function(tenantCol = NULL, indexedUserCol = NULL, indexedResCol = NULL, outputCol = NULL, userFactors = NULL, resFactors = NULL, scalerStats = NULL) {
+ml_access_anomaly_model <- function(tenantCol = NULL, indexedUserCol = NULL, indexedResCol = NULL, outputCol = NULL, userFactors = NULL, resFactors = NULL, scalerStats = NULL, device = NULL) {
   stage <- mmlspark_amd$models$cyber$AccessAnomalyModel()
   if (!is.null(tenantCol)) stage$set("tenantCol", tenantCol)
   if (!is.null(indexedUserCol)) stage$set("indexedUserCol", indexedUserCol)
@@ -26,6 +32,7 @@ ml_access_anomaly_model <- function(tenantCol = NULL, indexedUserCol = NULL, ind
   if (!is.null(userFactors)) stage$set("userFactors", userFactors)
   if (!is.null(resFactors)) stage$set("resFactors", resFactors)
   if (!is.null(scalerStats)) stage$set("scalerStats", scalerStats)
+  if (!is.null(device)) stage$set("device", device)
   stage
 }
 

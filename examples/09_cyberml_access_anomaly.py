@@ -48,3 +48,16 @@ normal = scored.anomaly_score[:2].mean()
 cross = scored.anomaly_score[2:].mean()
 print(f"\nmean normal={normal:.3f}  mean cross-team={cross:.3f}")
 assert cross > normal, "cross-team access should look more anomalous"
+
+# the reference's default mode: implicit-feedback ALS.  Access counts are the
+# likelihood, scaled per tenant into [5, 10]; no complement set is sampled.
+# device="auto" runs the fused HIP kernels when a GPU is present.
+counts = dfi.groupby(["tenant", "user_idx", "res_idx"], as_index=False).size()
+implicit = AccessAnomaly(maxIter=10, rankParam=8, applyImplicitCf=True,
+                         likelihoodCol="size", lowValue=5.0, highValue=10.0,
+                         device="auto").fit(counts)
+scored = implicit.transform(index(probe))
+normal = scored.anomaly_score[:2].mean()
+cross = scored.anomaly_score[2:].mean()
+print(f"implicit: mean normal={normal:.3f}  mean cross-team={cross:.3f}")
+assert cross > normal, "implicit mode should separate the teams too"

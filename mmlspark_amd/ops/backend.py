@@ -691,6 +691,150 @@ def sar_score_pairs(a_indptr, a_col, a_val, s_indptr, s_col, s_val, users,
                                    s_val, users, items)
 
 
+# ---------------------------------------------------------------------- ALS
+ALS_MAX_K = 64         # als_solve_rows_k pads the rank to 32 or 64
+
+
+def _check_als_factors(name, Y, like=None):
+    if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float32:
+        raise ValueError("als: %s must be a float32 tensor" % name)
+    if Y.dim() != 2 or not Y.is_contiguous():
+        raise ValueError("als: %s must be 2-D and contiguous" % name)
+    if not 1 <= Y.shape[1] <= ALS_MAX_K:
+        raise ValueError("als: the rank must lie in [1, %d]" % ALS_MAX_K)
+    if Y.shape[0] >= (1 << 31):
+        raise ValueError("als: %s must have fewer than 2^31 rows" % name)
+    if like is not None and Y.device != like.device:
+        raise ValueError("als: %s must live where the CSR arrays live" % name)
+
+
+def check_als_csr(indptr, col, val, n_cols, structure=True):
+    """A CSR matrix as the als kernels read it: int64 indptr (rows + 1), int32
+    col, float32 val, contiguous, on one device; with `structure` also indptr
+    from 0 to nnz without decreasing, columns inside [0, n_cols) and finite
+    values.  Columns may repeat and need no order inside a row.  Raises
+    ValueError; nothing is launched."""
+    def bad(msg):
+        raise ValueError("als: " + msg)
+
+    for what, t, dt in (("indptr", indptr, torch.int64),
+                        ("col", col, torch.int32), ("val", val, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            bad("%s must be a %s tensor" % (what, str(dt).split(".")[-1]))
+        if t.dim() != 1 or not t.is_contiguous():
+            bad(what + " must be 1-D and contiguous")
+        if t.device != indptr.device:
+            bad(what + " must live where indptr lives")
+    if indptr.numel() < 1 or indptr.numel() - 1 >= (1 << 31):
+        bad("indptr must hold rows + 1 entries, fewer than 2^31 rows")
+    if val.numel() != col.numel():
+        bad("val must hold one value per column index")
+    if not structure:
+        return
+    nnz = col.numel()
+    if int(indptr[0]) != 0 or int(indptr[-1]) != nnz:
+        bad("indptr must start at 0 and end at nnz")
+    if indptr.numel() > 1 and bool((indptr[1:] < indptr[:-1]).any()):
+        bad("indptr must not decrease")
+    if nnz:
+        if int(col.min()) < 0 or int(col.max()) >= int(n_cols):
+            bad("columns must lie in [0, %d)" % int(n_cols))
+        if not bool(torch.isfinite(val).all()):
+            bad("values must be finite")
+
+
+def _als_fused(t) -> bool:
+    """GPU tensors go to als_kernels.hip unless MMLSPARK_AMD_ALS_FUSED=0."""
+    import os
+    return t.is_cuda and os.environ.get("MMLSPARK_AMD_ALS_FUSED", "1") != "0"
+
+
+def als_gram(Y):
+    """Y^T Y as (k, k) float32.  On the device block partials are summed in a
+    fixed order in float64: the same bits on every call."""
+    _check_als_factors("Y", Y)
+    if _als_fused(Y):
+        return _require_ext().als_gram(Y)
+    return cpu_ref.als_gram(Y)
+
+
+def als_half_step(indptr, col, val, Y, reg, alpha, implicit, gram=None,
+                  heavy=0, check=True):
+    """One ALS half step: x (rows, k) float32 with A_u x_u = b_u for every row
+    u of the CSR matrix (indptr, col, val) against fixed factors Y (n_cols, k).
+    Explicit: A_u = sum_e y_e y_e^T + reg I, b_u = sum_e r_e y_e; every entry
+    counts, repeated columns included.  Implicit (Hu, Koren, Volinsky):
+    A_u = Y^T Y + sum_e alpha|r_e| y_e y_e^T + reg I, b_u = sum over r_e > 0 of
+    (1 + alpha|r_e|) y_e; `gram` = als_gram(Y) is computed when not given.
+    reg is not scaled by the row's count.  Rows without entries get 0.
+    `heavy` (0 = the kernels' default) is the degree above which a whole block
+    takes a row; a row's result does not change while it stays on its side.
+    check=False skips the O(nnz) structure check for a CSR checked before."""
+    _check_als_factors("Y", Y)
+    check_als_csr(indptr, col, val, Y.shape[0], check)
+    _check_als_factors("Y", Y, col)
+    if int(heavy) != heavy or heavy < 0:
+        raise ValueError("als: heavy must be an integer >= 0")
+    if not (reg >= 0 and alpha >= 0):
+        raise ValueError("als: reg and alpha must be >= 0")
+    k = Y.shape[1]
+    if implicit:
+        if gram is None:
+            gram = als_gram(Y)
+        elif (not isinstance(gram, torch.Tensor) or gram.dtype != torch.float32
+              or gram.shape != (k, k) or not gram.is_contiguous()
+              or gram.device != Y.device):
+            raise ValueError("als: gram must be a contiguous (k, k) float32 "
+                             "tensor beside Y")
+    else:
+        gram = None
+    if _als_fused(Y):
+        return _require_ext().als_half_step(indptr, col, val, Y, float(reg),
+                                            float(alpha), bool(implicit), gram,
+                                            int(heavy))
+    return cpu_ref.als_half_step(indptr, col, val, Y, float(reg), float(alpha),
+                                 bool(implicit), gram, int(heavy))
+
+
+def als_score_pairs(U, V, user, res, tenant, u_off, v_off, mean, std):
+    """Standardised anomaly scores (-(U_u . V_r) - mean_t) / std_t, float32
+    (n,), of pairs (user[p], res[p]) of tenant[p] (all int32).  U and V hold
+    the tenants' factor tables end to end; tenant t owns rows u_off[t] to
+    u_off[t + 1] of U and v_off[t] to v_off[t + 1] of V (int64, tenants + 1),
+    mean and std are float64 (tenants,).  A pair scores NaN when its tenant is
+    negative (unknown) or an index lies outside the tenant's tables."""
+    _check_als_factors("U", U)
+    _check_als_factors("V", V, U)
+    if U.shape[1] != V.shape[1]:
+        raise ValueError("als: U and V must share a rank")
+    n_t = mean.numel() if isinstance(mean, torch.Tensor) else -1
+    for what, t, dt, size in (
+            ("user", user, torch.int32, None), ("res", res, torch.int32, None),
+            ("tenant", tenant, torch.int32, None),
+            ("u_off", u_off, torch.int64, n_t + 1),
+            ("v_off", v_off, torch.int64, n_t + 1),
+            ("mean", mean, torch.float64, n_t), ("std", std, torch.float64, n_t)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 \
+                or not t.is_contiguous() or t.device != U.device:
+            raise ValueError("als: %s must be a contiguous 1-D %s tensor beside "
+                             "U" % (what, str(dt).split(".")[-1]))
+        if size is not None and t.numel() != size:
+            raise ValueError("als: %s must hold %d entries" % (what, size))
+    if not user.numel() == res.numel() == tenant.numel():
+        raise ValueError("als: user, res and tenant must pair up")
+    if n_t and (int(u_off[0]) != 0 or int(v_off[0]) != 0
+                or int(u_off[-1]) != U.shape[0] or int(v_off[-1]) != V.shape[0]
+                or bool((u_off[1:] < u_off[:-1]).any())
+                or bool((v_off[1:] < v_off[:-1]).any())):
+        raise ValueError("als: u_off and v_off must rise from 0 to the table "
+                         "sizes")
+    if _als_fused(U):
+        return _require_ext().als_score_pairs(U, V, user, res, tenant, u_off,
+                                              v_off, mean, std)
+    return cpu_ref.als_score_pairs(U, V, user, res, tenant, u_off, v_off, mean,
+                                   std)
+
+
 # ------------------------------------------------------------------- images
 JPEG_MAX_PIXELS = 1 << 26
 

@@ -886,6 +886,79 @@ def sar_score_pairs(a_indptr, a_col, a_val, s_indptr, s_col, s_val, users,
     return out
 
 
+# ----------------------------------------------------------------------- ALS
+# The contract of ops/hip/als_kernels.hip in float32 torch ops.  Per-entry
+# k x k products exist only for ALS_REF_BUDGET floats at a time.
+ALS_REF_BUDGET = 1 << 22
+
+
+def als_gram(Y):
+    """Y^T Y, (k, k) float32."""
+    return Y.t() @ Y
+
+
+def als_half_step(indptr, col, val, Y, reg, alpha, implicit, gram=None,
+                  heavy=0):
+    """x (rows, k): A_u x_u = b_u for every CSR row u against factors Y.
+    Explicit: A = sum y y^T + reg I, b = sum r y.  Implicit: A = gram +
+    sum alpha|r| y y^T + reg I, b = sum over r > 0 of (1 + alpha|r|) y.  Rows
+    without entries get 0.  `heavy` only steers the device kernels."""
+    dev = Y.device
+    n_rows, k = indptr.numel() - 1, Y.shape[1]
+    x = torch.zeros(n_rows, k, dtype=torch.float32, device=dev)
+    if n_rows == 0 or col.numel() == 0:
+        return x
+    if implicit:
+        w = float(alpha) * val.abs()
+        bw = torch.where(val > 0, 1.0 + w, torch.zeros_like(w))
+    else:
+        w, bw = None, val
+    eye = torch.eye(k, dtype=torch.float32, device=dev)
+    step = max(ALS_REF_BUDGET // (k * k), 1)      # entries, and rows, a pass
+    ptr = indptr.tolist()
+    r0 = 0
+    while r0 < n_rows:
+        r1 = min(r0 + step, n_rows)
+        while r1 > r0 + 1 and ptr[r1] - ptr[r0] > step:
+            r1 = r0 + max((r1 - r0) // 2, 1)
+        A = torch.zeros(r1 - r0, k, k, dtype=torch.float32, device=dev)
+        b = torch.zeros(r1 - r0, k, dtype=torch.float32, device=dev)
+        own_all = _csr_rows(indptr[r0:r1 + 1] - ptr[r0])
+        for e0 in range(ptr[r0], ptr[r1], step):
+            e1 = min(e0 + step, ptr[r1])
+            F = Y[col[e0:e1].long()]
+            own = own_all[e0 - ptr[r0]:e1 - ptr[r0]]
+            Fw = F if w is None else F * w[e0:e1, None]
+            A.index_add_(0, own, Fw.unsqueeze(2) * F.unsqueeze(1))
+            b.index_add_(0, own, F * bw[e0:e1, None])
+        if implicit:
+            A = A + gram
+        A = A + float(reg) * eye
+        empty = indptr[r0 + 1:r1 + 1] == indptr[r0:r1]
+        A[empty] = eye
+        b[empty] = 0
+        x[r0:r1] = torch.linalg.solve(A, b)
+        r0 = r1
+    return x
+
+
+def als_score_pairs(U, V, user, res, tenant, u_off, v_off, mean, std):
+    """(-(U[u_off[t] + user] . V[v_off[t] + res]) - mean[t]) / std[t] per pair,
+    float32; NaN where tenant < 0 or an index leaves the tenant's tables."""
+    n = user.numel()
+    out = torch.full((n,), float("nan"), dtype=torch.float32, device=U.device)
+    if n == 0 or mean.numel() == 0:
+        return out
+    t = tenant.long().clamp(0, mean.numel() - 1)
+    u, r = user.long(), res.long()
+    ok = ((tenant >= 0) & (tenant < mean.numel()) & (u >= 0) & (r >= 0)
+          & (u < u_off[t + 1] - u_off[t]) & (r < v_off[t + 1] - v_off[t]))
+    t, u, r = t[ok], u[ok], r[ok]
+    dot = (U[u_off[t] + u] * V[v_off[t] + r]).sum(dim=1)
+    out[ok] = ((-dot.double() - mean[t]) / std[t]).float()
+    return out
+
+
 # ------------------------------------------------------------- explainers
 def coalition_values(node_feature, node_threshold, node_left, node_right,
                      node_value, tree_offsets, tree_weights, X, bg, masks,

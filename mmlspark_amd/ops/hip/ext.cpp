@@ -107,6 +107,18 @@ int launch_coalition_values(const int*, const float*, const int*, const int*,
                             const unsigned*, int, int, const int*, int,
                             const float*, int, float, const int*, int, int,
                             double*, double*, hipStream_t);
+int als_heavy_degree();
+int als_gram_blocks(long);
+int launch_als_gram(const float*, long, int, float*, float*, hipStream_t);
+int launch_als_solve_rows(const long*, const int*, const float*, const float*,
+                          const float*, int, int, float, float, int, long,
+                          float*, hipStream_t);
+int launch_als_solve_heavy(const long*, const int*, const float*, const float*,
+                           const float*, const int*, int, int, float, float,
+                           int, float*, hipStream_t);
+int launch_als_score_pairs(const float*, const float*, const int*, const int*,
+                           const int*, const long*, const long*, const double*,
+                           const double*, int, int, long, float*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -949,6 +961,118 @@ torch::Tensor sar_score_pairs(
   return out;
 }
 
+// ---------------------------------------------------------------------- ALS
+// als_kernels.hip.  The CSR structure and the column range are checked by the
+// caller (ops/backend.py); shapes, dtypes and scalars here.
+static const int kAlsMaxK = 64;
+
+static void als_check_factors(const torch::Tensor& Y, const char* name) {
+  CHECK_DEV(Y); CHECK_CONTIG(Y);
+  TORCH_CHECK(Y.dtype() == torch::kFloat32 && Y.dim() == 2 && Y.size(1) >= 1 &&
+              Y.size(1) <= kAlsMaxK && Y.size(0) < (1L << 31), name,
+              " must be (n, k) float32 with 1 <= k <= ", kAlsMaxK);
+}
+
+// G = Y^T Y, (k, k) float32, the same bits on every call.
+torch::Tensor als_gram(torch::Tensor Y) {
+  als_check_factors(Y, "Y");
+  const long n = Y.size(0), k = Y.size(1);
+  if (n == 0) return torch::zeros({k, k}, Y.options());
+  const long K = k <= 32 ? 32 : 64;
+  auto partial = torch::empty({als_gram_blocks(n) * K * K}, Y.options());
+  auto G = torch::empty({k, k}, Y.options());
+  const int err = launch_als_gram(Y.data_ptr<float>(), n, (int)k,
+                                  partial.data_ptr<float>(),
+                                  G.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(err == 0, "als_gram launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return G;
+}
+
+// x (rows, k): the solutions of one ALS half step.  heavy = 0 takes the
+// kernels' ALS_HEAVY_DEGREE.
+torch::Tensor als_half_step(torch::Tensor indptr, torch::Tensor col,
+                            torch::Tensor val, torch::Tensor Y, double reg,
+                            double alpha, bool implicit,
+                            c10::optional<torch::Tensor> gram, long heavy) {
+  sar_check_csr(indptr, col, &val, "als");
+  als_check_factors(Y, "Y");
+  const long n_rows = indptr.numel() - 1, k = Y.size(1);
+  TORCH_CHECK(n_rows < (1L << 31), "too many rows");
+  TORCH_CHECK(heavy >= 0, "heavy must be >= 0");
+  const float* gp = nullptr;
+  if (implicit) {
+    TORCH_CHECK(gram.has_value(), "implicit mode needs gram = Y^T Y");
+    const auto& g = *gram;
+    CHECK_DEV(g); CHECK_CONTIG(g);
+    TORCH_CHECK(g.dtype() == torch::kFloat32 && g.dim() == 2 &&
+                g.size(0) == k && g.size(1) == k, "gram must be (k, k) float32");
+    gp = g.data_ptr<float>();
+  }
+  auto x = torch::empty({n_rows, k}, Y.options());
+  if (n_rows == 0) return x;
+  const long thr = heavy == 0 ? als_heavy_degree() : heavy;
+  int err = launch_als_solve_rows(
+      indptr.data_ptr<long>(), col.data_ptr<int>(), val.data_ptr<float>(),
+      Y.data_ptr<float>(), gp, (int)n_rows, (int)k, (float)reg, (float)alpha,
+      implicit ? 1 : 0, thr, x.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(err == 0, "als_solve_rows launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  auto degree = indptr.slice(0, 1) - indptr.slice(0, 0, n_rows);
+  auto heavy_rows = torch::nonzero(degree > thr).flatten().to(torch::kInt32);
+  if (heavy_rows.numel() > 0) {
+    err = launch_als_solve_heavy(
+        indptr.data_ptr<long>(), col.data_ptr<int>(), val.data_ptr<float>(),
+        Y.data_ptr<float>(), gp, heavy_rows.data_ptr<int>(),
+        (int)heavy_rows.numel(), (int)k, (float)reg, (float)alpha,
+        implicit ? 1 : 0, x.data_ptr<float>(), cur_stream());
+    TORCH_CHECK(err == 0, "als_solve_heavy launch failed: ",
+                hipGetErrorString((hipError_t)err));
+  }
+  return x;
+}
+
+// Standardised anomaly score of (user, res) pairs over the tenants' factor
+// tables laid end to end; NaN for tenant < 0 or an index outside its tables.
+torch::Tensor als_score_pairs(torch::Tensor U, torch::Tensor V,
+                              torch::Tensor user, torch::Tensor res,
+                              torch::Tensor tenant, torch::Tensor u_off,
+                              torch::Tensor v_off, torch::Tensor mean,
+                              torch::Tensor sd) {
+  for (const torch::Tensor* t : {&U, &V, &user, &res, &tenant, &u_off, &v_off,
+                                 &mean, &sd}) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous(),
+                "als_score_pairs arguments must be contiguous GPU tensors");
+  }
+  TORCH_CHECK(U.dtype() == torch::kFloat32 && V.dtype() == torch::kFloat32 &&
+              U.dim() == 2 && V.dim() == 2 && U.size(1) == V.size(1) &&
+              U.size(1) >= 1 && U.size(1) < (1L << 31),
+              "U and V must be (n, k) float32 of one rank");
+  const long n = user.numel(), T = mean.numel();
+  TORCH_CHECK(user.dtype() == torch::kInt32 && res.dtype() == torch::kInt32 &&
+              tenant.dtype() == torch::kInt32 && user.dim() == 1 &&
+              res.dim() == 1 && tenant.dim() == 1 && res.numel() == n &&
+              tenant.numel() == n, "user, res and tenant must be (n,) int32");
+  TORCH_CHECK(u_off.dtype() == torch::kInt64 && v_off.dtype() == torch::kInt64 &&
+              u_off.dim() == 1 && v_off.dim() == 1 && u_off.numel() == T + 1 &&
+              v_off.numel() == T + 1 && T < (1L << 31),
+              "u_off and v_off must be (tenants + 1,) int64");
+  TORCH_CHECK(mean.dtype() == torch::kFloat64 && sd.dtype() == torch::kFloat64 &&
+              mean.dim() == 1 && sd.dim() == 1 && sd.numel() == T,
+              "mean and std must be (tenants,) float64");
+  TORCH_CHECK(n < (1L << 39), "too many pairs for one launch");
+  auto out = torch::empty({n}, U.options());
+  if (n == 0) return out;
+  const int err = launch_als_score_pairs(
+      U.data_ptr<float>(), V.data_ptr<float>(), user.data_ptr<int>(),
+      res.data_ptr<int>(), tenant.data_ptr<int>(), u_off.data_ptr<long>(),
+      v_off.data_ptr<long>(), mean.data_ptr<double>(), sd.data_ptr<double>(),
+      (int)T, (int)U.size(1), n, out.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(err == 0, "als_score_pairs launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return out;
+}
+
 // --------------------------------------------------------------- explainers
 // explain_kernels.hip.  The contents of bidx and classes are range-checked by
 // the caller (ops/backend.py); the kernel clamps bidx and node features again,
@@ -1125,6 +1249,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("EXPLAIN_MAX_FEATURES") = kExplainMaxFeatures;
   m.attr("EXPLAIN_MAX_OUTPUTS") = kExplainMaxOutputs;
   m.attr("EXPLAIN_MAX_TILE_NODES") = kExplainMaxTileNodes;
+  m.def("als_gram", &als_gram, "Y^T Y in fixed summation order");
+  m.def("als_half_step", &als_half_step,
+        "one ALS half step: per-row normal equations formed and solved fused",
+        py::arg("indptr"), py::arg("col"), py::arg("val"), py::arg("Y"),
+        py::arg("reg"), py::arg("alpha"), py::arg("implicit"),
+        py::arg("gram") = py::none(), py::arg("heavy") = 0);
+  m.def("als_score_pairs", &als_score_pairs,
+        "standardised -U.V of (user, resource) pairs over tenant tables");
+  m.def("als_heavy_degree", &als_heavy_degree,
+        "row degree above which a whole block takes a row");
+  m.attr("ALS_MAX_K") = kAlsMaxK;
   m.attr("SAR_MAX_K") = kSarMaxK;
   m.attr("SAR_MAX_TILE") = kSarMaxTile;
 }
