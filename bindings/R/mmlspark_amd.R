@@ -1600,7 +1600,7 @@ ml_summarize_data <- function(counts = NULL, basic = NULL, percentiles = NULL) {
   stage
 }
 
-ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL) {
+ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, nIter = NULL, device = NULL) {
   stage <- mmlspark_amd$explainers$lime$SuperpixelTransformer()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1616,6 +1616,8 @@ ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClas
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(cellSize)) stage$set("cellSize", cellSize)
   if (!is.null(modifier)) stage$set("modifier", modifier)
+  if (!is.null(nIter)) stage$set("nIter", nIter)
+  if (!is.null(device)) stage$set("device", device)
   stage
 }
 

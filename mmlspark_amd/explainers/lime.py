@@ -7,14 +7,17 @@ sqrt(exp(-(d/width)^2)), LIMEBase.scala:55-65; per-row lasso :96-113).
 Output per row: (n_classes, m) coefficient matrix.
 With fusedSampling=True, TabularLIME and VectorLIME send each chunk's states
 and drawn background rows to the model's score_coalitions (GBDT models: one
-fused forest kernel, no perturbed samples) and fit the lasso on its output."""
+fused forest kernel, no perturbed samples) and fit the lasso on its output;
+ImageLIME segments uint8 images and builds the masked model input on the GPU
+(explainers/base.py), and SuperpixelTransformer(device="cuda") segments a
+whole column in batched launches."""
 from __future__ import annotations
 
 import numpy as np
 import pandas as pd
 import torch
 
-from ..core.param import Param, toFloat, toInt, toList
+from ..core.param import Param, toFloat, toInt, toList, toString
 from ..core.registry import register
 from ..core.schema import matrix_to_vector_column, vector_column_to_matrix
 from .base import LocalExplainer
@@ -201,15 +204,24 @@ class ImageLIME(LIMEBase):
         explanations, segs_col, r2s = [], [], []
         for _, row in df.iterrows():
             img = np.asarray(row[self.get("inputCol")])
-            segments = slic_superpixels(img, self.get("cellSize"),
-                                        self.get("modifier"))
+            fused = self._fused_image_model(img)
+            if fused is not None:
+                dev_img, seg = self._device_segments(fused, img)
+                segments = seg.cpu().numpy().astype(np.int64)
+            else:
+                segments = slic_superpixels(img, self.get("cellSize"),
+                                            self.get("modifier"))
             segs_col.append(segments)
             m = int(segments.max()) + 1
             n_samp = self.get("numSamples") or min(self._default_samples(m), 512)
             states = lime_sample_states(m, n_samp, rng)
-            imgs = ImageSampler(img, segments).apply(states)
-            scores = self._score_samples(
-                pd.DataFrame({self.get("inputCol"): imgs}))
+            if fused is not None:
+                scores = self._masked_image_scores(fused, dev_img, seg, m,
+                                                   states)
+            else:
+                imgs = ImageSampler(img, segments).apply(states)
+                scores = self._score_samples(
+                    pd.DataFrame({self.get("inputCol"): imgs}))
             explanations.append(self._fit_states(states, scores,
                                                  r2_out=r2s))
         out = df.copy()
@@ -227,11 +239,41 @@ class SuperpixelTransformer(LIMEBase):
     outputCol = Param("outputCol", "segment map column", "superpixels")
     cellSize = Param("cellSize", "superpixel cell size", 16, toInt)
     modifier = Param("modifier", "superpixel color weight", 10.0, toFloat)
+    nIter = Param("nIter", "k-means iterations", 5, toInt)
+    device = Param("device", "cpu|cuda|auto: on a GPU the uint8 images of "
+                   "the column are segmented together in batched kernel "
+                   "launches", "cpu", toString)
 
     def _transform(self, df: pd.DataFrame) -> pd.DataFrame:
+        from ..ops import backend
+        from ..utils.devices import default_device
+        cell, mod, n_iter = (self.get("cellSize"), self.get("modifier"),
+                             self.get("nIter"))
+        imgs = [np.asarray(v) for v in df[self.get("inputCol")].to_numpy()]
+        segs = [None] * len(imgs)
+        device = default_device(self.get("device"))
+        if device.type == "cuda":
+            # one upload and one set of launches for every image the kernels
+            # take; the rest keep the numpy function
+            on = [i for i, a in enumerate(imgs)
+                  if a.dtype == np.uint8
+                  and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] in (1, 3)))
+                  and max(a.shape[:2]) <= backend.SLIC_MAX_DIM
+                  and 1 <= backend.slic_num_centers(
+                      a.shape[0], a.shape[1], cell) <= backend.SLIC_MAX_K]
+            if on:
+                flat = torch.from_numpy(np.concatenate(
+                    [imgs[i].reshape(-1) for i in on])).to(device)
+                views = [v.view(imgs[i].shape) for v, i in zip(
+                    flat.split([imgs[i].size for i in on]), on)]
+                labels, _ = backend.slic_segment(views, cell, mod, n_iter)
+                sizes = [v.numel() for v in labels]
+                host = torch.cat([v.reshape(-1) for v in labels]).cpu() \
+                    .numpy().astype(np.int64)
+                for i, v in zip(on, np.split(host, np.cumsum(sizes)[:-1])):
+                    segs[i] = v.reshape(imgs[i].shape[:2])
         out = df.copy()
         out[self.get("outputCol")] = [
-            slic_superpixels(np.asarray(v), self.get("cellSize"),
-                             self.get("modifier"))
-            for v in df[self.get("inputCol")].to_numpy()]
+            slic_superpixels(a, cell, mod, n_iter) if s is None else s
+            for a, s in zip(imgs, segs)]
         return out

@@ -14,7 +14,8 @@ With fusedSampling=True, TabularSHAP and VectorSHAP hand the coalitions, the
 background and the drawn background rows to the model's score_coalitions
 (GBDT models: one fused forest kernel per chunk, the perturbed samples never
 built); only the background and the explained rows themselves are still
-scored through score_matrix.
+scored through score_matrix.  ImageSHAP with fusedSampling=True segments uint8
+images and builds the masked model input on the GPU (explainers/base.py).
 Output per row: (n_classes, m+1) — [base_value, phi_1..phi_m] per class."""
 from __future__ import annotations
 
@@ -253,21 +254,32 @@ class ImageSHAP(KernelSHAPBase):
         explanations, segs_col = [], []
         for _, row in df.iterrows():
             img = np.asarray(row[self.get("inputCol")])
-            segments = slic_superpixels(img, self.get("cellSize"),
-                                        float(self.get("modifier")))
+            fused = self._fused_image_model(img)
+            if fused is not None:
+                dev_img, seg = self._device_segments(fused, img)
+                segments = seg.cpu().numpy().astype(np.int64)
+            else:
+                segments = slic_superpixels(img, self.get("cellSize"),
+                                            float(self.get("modifier")))
             segs_col.append(segments)
             m = int(segments.max()) + 1
             n_samp = self.get("numSamples") or min(self._default_samples(m), 2048)
             Z, w = sample_coalitions(m, n_samp, rng)
-            sampler = ImageSampler(img, segments)
-            imgs = sampler.apply(Z)
-            blank = np.zeros_like(img)
-            samples_df = pd.DataFrame({
-                self.get("inputCol"): imgs + [blank, img]})
-            scores = self._score_samples(samples_df)
-            v = scores[:len(imgs)]
-            v_null = scores[len(imgs)]
-            v_full = scores[len(imgs) + 1]
+            if fused is not None:
+                # the blank and the full image are the all-off and all-on
+                # rows of the same launch
+                scores = self._masked_image_scores(
+                    fused, dev_img, seg, m, np.concatenate(
+                        [Z, np.zeros((1, m), Z.dtype), np.ones((1, m), Z.dtype)]))
+            else:
+                imgs = ImageSampler(img, segments).apply(Z)
+                blank = np.zeros_like(img)
+                samples_df = pd.DataFrame({
+                    self.get("inputCol"): imgs + [blank, img]})
+                scores = self._score_samples(samples_df)
+            v = scores[:len(Z)]
+            v_null = scores[len(Z)]
+            v_full = scores[len(Z) + 1]
             explanations.append(self._solve(Z, v, w, v_null, v_full))
         out = df.copy()
         out[self.get("outputCol")] = explanations

@@ -185,6 +185,26 @@ class TorchModel(Model):
         return torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32)
                                           for v in vals]))
 
+    def image_input_size(self, shape) -> int:
+        """Side of the square input _coerce makes of an image of `shape`."""
+        return int(max(shape[:2]))
+
+    def score_image_batch(self, batch: torch.Tensor) -> np.ndarray:
+        """The (n, outputs) float32 matrix _transform writes to outputCol for
+        a ready (n, 3, S, S) float32 batch on the model's device, forwarded in
+        the same batchSize chunks under no_grad: no rows, no DataFrame."""
+        device = default_device(self.get("device"))
+        self.module.to(device).eval()
+        bs = self.get("batchSize")
+        outs = []
+        with torch.no_grad():
+            for s in range(0, len(batch), bs):
+                outs.append(self._forward(batch[s:s + bs].to(device))
+                            .detach().float())
+        if not outs:
+            return np.zeros((0, 0), np.float32)
+        return torch.cat(outs).cpu().numpy().reshape(len(batch), -1)
+
     def _transform(self, df: pd.DataFrame) -> pd.DataFrame:
         device = default_device(self.get("device"))
         mod = self.module.to(device).eval()
@@ -246,6 +266,9 @@ class ImageFeaturizer(TorchModel):
 
     def _forward(self, batch):
         return self.module(batch, cut_output_layers=self.get("cutOutputLayers"))
+
+    def image_input_size(self, shape) -> int:
+        return self.get("imageSize")
 
     def _coerce(self, vals):
         size = self.get("imageSize")

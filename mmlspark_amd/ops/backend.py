@@ -1052,3 +1052,138 @@ def image_preprocess(src, idesc, fdesc, work_off, out):
             work_off.to(dev, non_blocking=True), int(work_off[-1]), out)
         return out
     return cpu_ref.image_preprocess(src, idesc, fdesc, work_off, out)
+
+
+# -------------------------------------------------------------- superpixels
+SLIC_MAX_K, SLIC_MAX_DIM = cpu_ref.SLIC_MAX_K, cpu_ref.SLIC_MAX_DIM
+slic_num_centers = cpu_ref.slic_num_centers
+pack_states = cpu_ref.pack_states
+
+
+def _image_explain_fused(t) -> bool:
+    """GPU tensors go to superpixel_kernels.hip unless
+    MMLSPARK_AMD_IMAGE_EXPLAIN_FUSED=0."""
+    import os
+    return t.is_cuda and os.environ.get(
+        "MMLSPARK_AMD_IMAGE_EXPLAIN_FUSED", "1") != "0"
+
+
+def _check_u8_image(what, t, like=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 \
+            or not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] in (1, 3))):
+        raise ValueError(what + ": images must be uint8 tensors (H, W), "
+                         "(H, W, 1) or (H, W, 3)")
+    if min(t.shape[:2]) < 1 or max(t.shape[:2]) > SLIC_MAX_DIM \
+            or t.shape[0] * t.shape[1] >= (1 << 31):
+        raise ValueError(what + ": image sides must lie in [1, %d] with "
+                         "H * W < 2^31" % SLIC_MAX_DIM)
+    if like is not None and t.device != like.device:
+        raise ValueError(what + ": all tensors must share a device")
+
+
+def slic_segment(images, cell_size=16, modifier=10.0, n_iter=5, centers=None):
+    """SLIC superpixels (explainers/sampler.py::slic_superpixels) of a list of
+    uint8 images of any mix of sizes on one device: returns the labels of the
+    last assignment, one (H, W) int32 tensor per image, and the centres after
+    the last update, one (K, 5) float32 tensor per image.  cell_size is one
+    int for all images or one per image.  `centers` gives one
+    (K, 5) float32 start per image in place of the grid seeds, which lets an
+    iteration be driven from outside.  On the GPU the whole list is two
+    launches per iteration; an image has at most SLIC_MAX_K centres and sides
+    of at most SLIC_MAX_DIM.  The means are exact integer sums divided once
+    (cpu_ref.slic_segment), where numpy's float32 mean rounds per addition."""
+    images = list(images)
+    n_iter = int(n_iter)
+    cells = [int(c) for c in cell_size] if hasattr(cell_size, "__len__") \
+        else [int(cell_size)] * len(images)
+    if len(cells) != len(images) or any(c < 1 for c in cells) or n_iter < 0 \
+            or not float(modifier) > 0:
+        raise ValueError("slic_segment: cell size and modifier must be "
+                         "positive and n_iter >= 0")
+    if not images:
+        return [], []
+    ks = []
+    for t, cell in zip(images, cells):
+        _check_u8_image("slic_segment", t, images[0])
+        ks.append(slic_num_centers(t.shape[0], t.shape[1], cell))
+        if not 1 <= ks[-1] <= SLIC_MAX_K:
+            raise ValueError("slic_segment: an image must have between 1 and "
+                             "%d centres, got %d" % (SLIC_MAX_K, ks[-1]))
+    if centers is not None:
+        centers = list(centers)
+        if len(centers) != len(images) or any(
+                not isinstance(c, torch.Tensor) or c.dtype != torch.float32
+                or tuple(c.shape) != (k, 5) or c.device != images[0].device
+                for c, k in zip(centers, ks)):
+            raise ValueError("slic_segment: centers must hold one (K, 5) "
+                             "float32 tensor per image beside the images")
+    if not _image_explain_fused(images[0]):
+        dev = images[0].device
+        lab, ctr = cpu_ref.slic_segment(
+            [t.cpu() for t in images], cells, float(modifier), n_iter,
+            None if centers is None else [c.cpu() for c in centers])
+        return [v.to(dev) for v in lab], [c.to(dev) for c in ctr]
+    sizes = [t.numel() for t in images]
+    offs = [0]
+    for s in sizes:
+        offs.append(offs[-1] + s)
+    shapes = torch.tensor(
+        [[o, t.shape[0], t.shape[1], 1 if t.dim() == 2 else t.shape[2], c]
+         for o, t, c in zip(offs, images, cells)], dtype=torch.int64)
+    src = torch.cat([t.reshape(-1) for t in images])
+    lab, ctr = _require_ext().slic_segment(
+        src, shapes, None if centers is None else torch.cat(centers),
+        float(modifier), n_iter)
+    npix = [t.shape[0] * t.shape[1] for t in images]
+    labels = [v.view(t.shape[0], t.shape[1])
+              for v, t in zip(lab.split(npix), images)]
+    return labels, list(ctr.split(ks))
+
+
+def masked_image_batch(image, segments, states, fill, size, lut, m=None):
+    """The model input of every perturbed sample of one image, (n, 3, size,
+    size) float32 on the image's device: what _rows_to_batch makes of
+    ImageSampler.apply's images.  image is uint8 (H, W[, 1|3]), segments its
+    int32 (H, W) map, states the samples' bit rows from pack_states, int32
+    (n, ceil(m / 32)), fill the uint8 value of switched-off segments and lut
+    the 256-entry k / 255 table.  m defaults to segments.max() + 1 and is at
+    most SLIC_MAX_K.  When the image is not size x size it is resized as
+    torch's bilinear interpolate (align_corners=False) does, every tap masked
+    by its own pixel's segment.
+
+    One difference from the host path: _rows_to_batch divides a sample by 255
+    only if that sample's maximum exceeds 1.5, this always reads uint8 as
+    0..255.  The two differ only for a sample whose surviving pixels are all
+    0 or 1."""
+    _check_u8_image("masked_image_batch", image)
+    h, w = image.shape[:2]
+    for what, t, dt, shape in (("segments", segments, torch.int32, (h, w)),
+                               ("states", states, torch.int32, None),
+                               ("lut", lut, torch.float32, (256,))):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt \
+                or t.device != image.device \
+                or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError("masked_image_batch: %s must be a %s tensor%s "
+                             "beside the image" % (
+                                 what, str(dt).split(".")[-1],
+                                 "" if shape is None else " " + str(shape)))
+    if m is None:
+        m = int(segments.max()) + 1
+    m, fill, size = int(m), int(fill), int(size)
+    if not 1 <= m <= SLIC_MAX_K:
+        raise ValueError("masked_image_batch: segment count must lie in "
+                         "[1, %d]" % SLIC_MAX_K)
+    if states.dim() != 2 or states.shape[1] != (m + 31) // 32:
+        raise ValueError("masked_image_batch: states must be (n, ceil(m / "
+                         "32)) bit rows")
+    if not 0 <= fill <= 255 or not 1 <= size <= SLIC_MAX_DIM:
+        raise ValueError("masked_image_batch: fill must lie in [0, 255] and "
+                         "size in [1, %d]" % SLIC_MAX_DIM)
+    if _image_explain_fused(image):
+        return _require_ext().masked_image_batch(
+            image.contiguous(), segments.contiguous(), states.contiguous(), m,
+            fill, size, lut.contiguous())
+    dev = image.device
+    return cpu_ref.masked_image_batch(image.cpu(), segments.cpu(),
+                                      states.cpu(), m, fill, size,
+                                      lut.cpu()).to(dev)

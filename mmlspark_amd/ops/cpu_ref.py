@@ -1011,3 +1011,103 @@ def coalition_values(node_feature, node_threshold, node_left, node_right,
             vals = vals[:, list(classes)].reshape(z1 - z0, B, C)
             out[r, z0:z1] = vals.sum(dim=1) / float(B)
     return out
+
+
+# ------------------------------------------------------------- superpixels
+# The contract of ops/hip/superpixel_kernels.hip.
+SLIC_MAX_K = 4096
+SLIC_MAX_DIM = 32768
+
+
+def slic_num_centers(H, W, cell):
+    """Centres slic_superpixels seeds on an H x W image: the grid
+    cell // 2, + cell, ... along both axes."""
+    return len(range(cell // 2, H, cell)) * len(range(cell // 2, W, cell))
+
+
+def slic_segment(images, cells, modifier, n_iter=5, centers=None):
+    """explainers/sampler.py::slic_superpixels over a list of uint8 images
+    (H, W), (H, W, 1) or (H, W, 3), each with its cell size, in float32 numpy a block of pixels at a
+    time: five features [r, g, b] / modifier, y / cell, x / cell; every pixel
+    goes to the nearest of all K centres, distance ((((dr^2 + dg^2) + db^2) +
+    dy^2) + dx^2), ties to the lowest index; non-empty clusters move to their
+    mean, taken as exact integer sums of r, g, b, y, x over the count, divided
+    in float64 and rounded to float32 once (numpy's float32 mean of the
+    features lies within a few ulp of it).  `centers` gives one (K, 5) float32
+    start per image in place of the grid seeds.  Returns the labels of the last
+    assignment, (H, W) int32 per image, and the centres after the last
+    update."""
+    import numpy as np
+    labels, out_centers = [], []
+    mod = np.float32(modifier)
+    for i, (image, cell) in enumerate(zip(images, cells)):
+        fcell = np.float32(cell)
+        a = image.numpy()
+        h, w = a.shape[:2]
+        rgb = np.broadcast_to(a.reshape(h, w, -1), (h, w, 3)).reshape(-1, 3)
+        yy, xx = np.divmod(np.arange(h * w), w)
+        ints = np.concatenate([rgb.astype(np.int64), yy[:, None], xx[:, None]],
+                              axis=1)
+        feats = ints.astype(np.float32) / np.array([mod] * 3 + [fcell] * 2)
+        if centers is None:
+            gy = np.arange(cell // 2, h, cell)
+            gx = np.arange(cell // 2, w, cell)
+            c = feats[(gy[:, None] * w + gx[None, :]).reshape(-1)].copy()
+        else:
+            c = centers[i].numpy().astype(np.float32).copy()
+        k = len(c)
+        lab = np.zeros(h * w, dtype=np.int32)
+        for _ in range(n_iter):
+            for p0 in range(0, h * w, 4096):
+                d = feats[p0:p0 + 4096, None, :] - c[None, :, :]
+                d = d * d
+                d = (((d[..., 0] + d[..., 1]) + d[..., 2]) + d[..., 3]) \
+                    + d[..., 4]
+                lab[p0:p0 + 4096] = d.argmin(1)
+            cnt = np.bincount(lab, minlength=k)
+            sums = np.stack([np.bincount(lab, weights=ints[:, q], minlength=k)
+                             for q in range(5)], axis=1)   # exact in float64
+            full = cnt > 0
+            scale = np.array([float(mod)] * 3 + [float(fcell)] * 2)
+            c[full] = (sums[full] / cnt[full, None] / scale).astype(np.float32)
+        labels.append(torch.from_numpy(lab.reshape(h, w)))
+        out_centers.append(torch.from_numpy(c))
+    return labels, out_centers
+
+
+def pack_states(states):
+    """On/off states (n, m), on where >= 0.5, as int32 bit rows
+    (n, ceil(m / 32)): segment j is bit j % 32 of word j // 32."""
+    import numpy as np
+    on = np.asarray(states) >= 0.5
+    n, m = on.shape
+    words = (m + 31) // 32
+    bits = np.zeros((n, words * 32), dtype=np.uint8)
+    bits[:, :m] = on
+    packed = np.packbits(bits.reshape(n, words, 32), axis=2,
+                         bitorder="little")
+    return torch.from_numpy(packed.view("<u4").reshape(n, words).astype(np.int32))
+
+
+def masked_image_batch(image, segments, states, m, fill, size, lut):
+    """(n, 3, size, size) float32: for every bit row of `states` the uint8
+    image with the segments whose bit is clear set to `fill` (a segment
+    outside [0, m) is never off), gray replicated to three channels, mapped
+    through lut (k / 255), CHW, then torch's bilinear resize
+    (align_corners=False) when the image is not size x size, so every tap is
+    masked by its own pixel's segment."""
+    n = states.shape[0]
+    h, w = image.shape[:2]
+    bits = ((states.long().unsqueeze(-1) >> torch.arange(32)) & 1).bool()
+    bits = bits.reshape(n, -1)
+    seg = segments.long()
+    inside = (seg >= 0) & (seg < m)
+    on = bits[:, seg.clamp(0, bits.shape[1] - 1)] | ~inside       # (n, H, W)
+    img = image.reshape(h, w, -1).expand(h, w, 3)
+    masked = torch.where(on.unsqueeze(-1), img,
+                         torch.tensor(fill, dtype=torch.uint8))
+    batch = lut[masked.long()].permute(0, 3, 1, 2).contiguous()
+    if h != size or w != size:
+        batch = torch.nn.functional.interpolate(
+            batch, size=(size, size), mode="bilinear", align_corners=False)
+    return batch

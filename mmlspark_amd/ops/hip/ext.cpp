@@ -119,6 +119,12 @@ int launch_als_solve_heavy(const long*, const int*, const float*, const float*,
 int launch_als_score_pairs(const float*, const float*, const int*, const int*,
                            const int*, const long*, const long*, const double*,
                            const double*, int, int, long, float*, hipStream_t);
+int launch_slic_segment(const unsigned char*, long, const long*, const long*,
+                        int, long, int, long, float*, unsigned long long*,
+                        int*, long, float, int, int, hipStream_t);
+int launch_masked_image_batch(const unsigned char*, int, int, int, const int*,
+                              const unsigned*, int, int, int, int, int,
+                              const float*, float*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -1192,6 +1198,158 @@ torch::Tensor coalition_values(
   return out;
 }
 
+// ---------------------------------------------------------------- superpixels
+// superpixel_kernels.hip.  Limits: at most kSlicMaxK centres per image; image
+// sides at most kSlicMaxDim, which keeps a block's 32-bit LDS partial sums
+// (at most 1024 pixels of at most max(255, side - 1) each) below 2^25; and
+// H * W < 2^31.
+static const int kSlicMaxK = 4096;
+static const int kSlicMaxDim = 32768;
+
+// Grid seeds along one axis: cell/2, cell/2 + cell, ... below n.
+static long slic_grid(long n, long cell) {
+  return n > cell / 2 ? (n - cell / 2 + cell - 1) / cell : 0;
+}
+
+static long slic_num_centers(long H, long W, long cell) {
+  TORCH_CHECK(cell >= 1, "slic_segment: cell size must be positive");
+  return slic_grid(H, cell) * slic_grid(W, cell);
+}
+
+// src: the column's pixels end to end, uint8 on the GPU.  shapes: CPU int64
+// (n_img, 5) rows {byte offset into src, H, W, C, cell size}.  centres: optional
+// (total K, 5) float32 start centres, image after image; seeded from the grid
+// when absent.  Returns the labels of the last assignment, (total pixels,)
+// int32, and the centres after the last update, (total K, 5) float32.
+std::tuple<torch::Tensor, torch::Tensor> slic_segment(
+    torch::Tensor src, torch::Tensor shapes,
+    c10::optional<torch::Tensor> centres, double modifier, long n_iter) {
+  CHECK_DEV(src); CHECK_CONTIG(src);
+  TORCH_CHECK(src.dtype() == torch::kUInt8 && src.dim() == 1,
+              "slic_segment: src must be a flat uint8 buffer");
+  TORCH_CHECK(!shapes.is_cuda() && shapes.dtype() == torch::kInt64 &&
+              shapes.dim() == 2 && shapes.size(1) == 5 &&
+              shapes.is_contiguous(),
+              "slic_segment: shapes must be a CPU int64 (n, 5) tensor");
+  TORCH_CHECK(modifier > 0 && std::isfinite((float)modifier) &&
+              (float)modifier > 0.f,
+              "slic_segment: modifier must be positive and finite");
+  TORCH_CHECK(n_iter >= 0 && n_iter <= 1000,
+              "slic_segment: n_iter must lie in [0, 1000]");
+  const long n = shapes.size(0);
+  TORCH_CHECK(n < (1L << 20), "slic_segment: too many images for one launch");
+  auto desc = torch::empty({n * 8 + n + 1}, shapes.options());
+  long* d = desc.data_ptr<long>();
+  long* wo = d + n * 8;
+  const long* s = shapes.data_ptr<long>();
+  long total_k = 0, total_pix = 0, items = 0, max_k = 0;
+  for (long i = 0; i < n; ++i) {
+    const long off = s[5 * i], H = s[5 * i + 1], W = s[5 * i + 2],
+               C = s[5 * i + 3], cell = s[5 * i + 4];
+    TORCH_CHECK(cell >= 1 && cell <= kSlicMaxDim,
+                "slic_segment: cell size out of range");
+    TORCH_CHECK(H >= 1 && W >= 1 && H <= kSlicMaxDim && W <= kSlicMaxDim &&
+                H * W < (1L << 31),
+                "slic_segment: image sides must lie in [1, ", kSlicMaxDim,
+                "] (the 32-bit LDS partial sums) with H * W < 2^31");
+    TORCH_CHECK(C == 1 || C == 3, "slic_segment: images have 1 or 3 channels");
+    TORCH_CHECK(off >= 0 && off + H * W * C <= src.numel(),
+                "slic_segment: image runs past the source buffer");
+    const long K = slic_num_centers(H, W, cell);
+    TORCH_CHECK(K >= 1 && K <= kSlicMaxK, "slic_segment: an image must have "
+                "between 1 and ", kSlicMaxK, " centres, got ", K);
+    long* q = d + 8 * i;
+    q[0] = off; q[1] = H; q[2] = W; q[3] = C; q[4] = K; q[5] = total_k;
+    q[6] = total_pix; q[7] = cell;
+    wo[i] = items;
+    total_k += K;
+    total_pix += H * W;
+    items += (H * W + 1023) / 1024;
+    max_k = std::max(max_k, K);
+  }
+  wo[n] = items;
+  TORCH_CHECK(items < (1L << 31), "slic_segment: column too large for one "
+              "launch");
+  // without an iteration nothing is assigned: every label is 0
+  auto lopt = src.options().dtype(torch::kInt32);
+  auto labels = n_iter == 0 ? torch::zeros({total_pix}, lopt)
+                            : torch::empty({total_pix}, lopt);
+  torch::Tensor ctr;
+  if (centres.has_value()) {
+    TORCH_CHECK(centres->is_cuda() && centres->device() == src.device() &&
+                centres->dtype() == torch::kFloat32 && centres->dim() == 2 &&
+                centres->size(0) == total_k && centres->size(1) == 5,
+                "slic_segment: centres must be (total K, 5) float32 beside "
+                "src");
+    ctr = centres->contiguous().clone();
+  } else {
+    ctr = torch::empty({total_k, 5}, src.options().dtype(torch::kFloat32));
+  }
+  if (n == 0) return {labels, ctr};
+  auto sums = torch::zeros({total_k, 6}, src.options().dtype(torch::kInt64));
+  auto ddesc = desc.to(src.device());
+  const long* dd = ddesc.data_ptr<long>();
+  const int err = launch_slic_segment(
+      src.data_ptr<uint8_t>(), src.numel(), dd, dd + n * 8, (int)n, items,
+      (int)max_k, total_k, ctr.data_ptr<float>(),
+      (unsigned long long*)sums.data_ptr<int64_t>(), labels.data_ptr<int>(),
+      total_pix, (float)modifier, (int)n_iter,
+      centres.has_value() ? 0 : 1, cur_stream());
+  TORCH_CHECK(err == 0, "slic_segment launch failed: ",
+              err < 0 ? "argument out of range"
+                      : hipGetErrorString((hipError_t)err));
+  return {labels, ctr};
+}
+
+// (n, 3, size, size) float32: sample s is the image with every segment whose
+// bit in states[s] is clear replaced by `fill`, gray replicated, mapped
+// through lut, CHW, and resized bilinearly when the image is not size x size.
+torch::Tensor masked_image_batch(torch::Tensor img, torch::Tensor seg,
+                                 torch::Tensor states, long m, long fill,
+                                 long size, torch::Tensor lut) {
+  for (const torch::Tensor* t : {&img, &seg, &states, &lut}) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->device() == img.device(), "masked_image_batch arguments "
+                "must be contiguous tensors on one GPU");
+  }
+  TORCH_CHECK(img.dtype() == torch::kUInt8 &&
+              (img.dim() == 2 || (img.dim() == 3 && (img.size(2) == 1 ||
+                                                     img.size(2) == 3))),
+              "masked_image_batch: image must be uint8 (H, W) or (H, W, 1|3)");
+  const long H = img.size(0), W = img.size(1);
+  const long C = img.dim() == 3 ? img.size(2) : 1;
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= kSlicMaxDim && W <= kSlicMaxDim &&
+              H * W < (1L << 31), "masked_image_batch: image too large");
+  TORCH_CHECK(seg.dtype() == torch::kInt32 && seg.dim() == 2 &&
+              seg.size(0) == H && seg.size(1) == W,
+              "masked_image_batch: segments must be int32 (H, W)");
+  TORCH_CHECK(m >= 1 && m <= kSlicMaxK,
+              "masked_image_batch: segment count must lie in [1, ", kSlicMaxK,
+              "]");
+  TORCH_CHECK(states.dtype() == torch::kInt32 && states.dim() == 2 &&
+              states.size(1) == (m + 31) / 32 && states.size(0) < (1L << 31),
+              "masked_image_batch: states must be int32 (n, ceil(m / 32))");
+  TORCH_CHECK(fill >= 0 && fill <= 255,
+              "masked_image_batch: fill must lie in [0, 255]");
+  TORCH_CHECK(size >= 1 && size <= kSlicMaxDim && size * size < (1L << 31),
+              "masked_image_batch: size out of range");
+  TORCH_CHECK(lut.dtype() == torch::kFloat32 && lut.numel() == 256,
+              "masked_image_batch: lut must hold 256 float32 values");
+  const long n = states.size(0);
+  auto out = torch::empty({n, 3, size, size},
+                          img.options().dtype(torch::kFloat32));
+  if (n == 0) return out;
+  const int err = launch_masked_image_batch(
+      img.data_ptr<uint8_t>(), (int)H, (int)W, (int)C, seg.data_ptr<int>(),
+      (const unsigned*)states.data_ptr<int>(), (int)n, (int)states.size(1),
+      (int)m, (int)fill, (int)size, lut.data_ptr<float>(),
+      out.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(err == 0, "masked_image_batch launch failed: ",
+              err < 0 ? "argument out of range"
+                      : hipGetErrorString((hipError_t)err));
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -1259,6 +1417,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "standardised -U.V of (user, resource) pairs over tenant tables");
   m.def("als_heavy_degree", &als_heavy_degree,
         "row degree above which a whole block takes a row");
+  m.def("slic_segment", &slic_segment,
+        "SLIC superpixels of a column of uint8 images, exact integer means",
+        py::arg("src"), py::arg("shapes"), py::arg("centres") = py::none(),
+        py::arg("modifier") = 10.0, py::arg("n_iter") = 5);
+  m.def("slic_num_centers", &slic_num_centers,
+        "grid-seeded centres of an H x W image at a cell size");
+  m.def("masked_image_batch", &masked_image_batch,
+        "masked samples of one image as the model's float32 NCHW batch");
+  m.attr("SLIC_MAX_K") = kSlicMaxK;
+  m.attr("SLIC_MAX_DIM") = kSlicMaxDim;
   m.attr("ALS_MAX_K") = kAlsMaxK;
   m.attr("SAR_MAX_K") = kSarMaxK;
   m.attr("SAR_MAX_TILE") = kSarMaxTile;
