@@ -94,6 +94,58 @@ def _filter_csr(idx, val, off, mask):
     return idx[e], val[e], new_off
 
 
+def _extract_compact(df: pd.DataFrame, cols, device="cpu"):
+    """Feature columns -> the compact namespace batch of the vw_*_interact
+    kernels: raw per-column indices (unseeded, unmasked), values, ns_off
+    (n, len(cols) + 1) bounding each column's entries within each row, and
+    the per-column seeds that _extract_csr would add."""
+    from .murmur import hash_string
+    n = len(df)
+    counts = np.zeros((n, len(cols)), dtype=np.int64)
+    per_col = []
+    for ci, c in enumerate(cols):
+        ii, vv = [], []
+        for r, v in enumerate(df[c].to_numpy()):
+            if isinstance(v, SparseVector):
+                ii.append(v.indices)
+                vv.append(v.values)
+            else:
+                dense = np.asarray(v, dtype=np.float32)
+                nz = np.nonzero(dense)[0]
+                ii.append(nz)
+                vv.append(dense[nz])
+            counts[r, ci] = len(ii[-1])
+        per_col.append((np.concatenate(ii) if ii else np.zeros(0, np.int64),
+                        np.concatenate(vv) if vv else np.zeros(0, np.float32)))
+    ns_off = np.zeros((n, len(cols) + 1), dtype=np.int64)
+    ns_off[:, 1:] = np.cumsum(counts.reshape(-1)).reshape(counts.shape)
+    ns_off[1:, 0] = ns_off[:-1, -1]
+    total = int(ns_off[-1, -1]) if n else 0
+    indices = np.zeros(total, dtype=np.int32)
+    values = np.zeros(total, dtype=np.float32)
+    for ci, (ic, vc) in enumerate(per_col):
+        first = np.cumsum(counts[:, ci]) - counts[:, ci]
+        within = np.arange(len(ic)) - np.repeat(first, counts[:, ci])
+        dst = np.repeat(ns_off[:, ci], counts[:, ci]) + within
+        indices[dst] = ic.astype(np.int32)
+        values[dst] = vc.astype(np.float32)
+    seeds = np.array([0 if ci == 0 else hash_string(c) & 0x3FFFFFFF
+                      for ci, c in enumerate(cols)], dtype=np.int32)
+    return (torch.from_numpy(indices).to(device),
+            torch.from_numpy(values).to(device),
+            torch.from_numpy(ns_off).to(device),
+            torch.from_numpy(seeds).to(device))
+
+
+def _filter_compact(idx, val, ns_off, mask):
+    """_filter_csr for a compact namespace batch: keeps ns_off's columns."""
+    starts = ns_off[mask, 0]
+    off = torch.cat([ns_off[:, 0], ns_off[-1:, -1]]) if len(ns_off) \
+        else ns_off.new_zeros(1)
+    fi, fv, new_off = _filter_csr(idx, val, off, mask)
+    return fi, fv, ns_off[mask] - (starts - new_off[:-1])[:, None]
+
+
 def _avg_loss(pred: torch.Tensor, y: torch.Tensor, loss: str) -> float:
     if loss == "logistic":
         ll = torch.log1p(torch.exp(-y * pred))
@@ -144,6 +196,17 @@ class _VWParams(Params):
     interactions = Param("interactions", "feature-column groups to cross "
                          "with VW's FNV hash-combine (estimator-level -q): "
                          "each entry a list or 'colA,colB' string", None)
+    fusedInteractions = Param(
+        "fusedInteractions", "cross two-column interactions (-q) inside the "
+        "SGD and predict kernels instead of materialising them on the host: "
+        "the device holds each feature column once.  One semantic "
+        "difference: crossed features of a row that collide on a table slot "
+        "stay separate features and are not pre-summed; predictions of a "
+        "given table are unaffected, SGD trajectories differ only for rows "
+        "with such collisions.  Specs with other than two columns, columns "
+        "outside featuresCol/additionalFeatures, more pairs than the kernel "
+        "takes, --bfgs and the contextual bandit use the materialised path",
+        False, toBool)
     ignoreNamespaces = Param("ignoreNamespaces", "first-letter namespaces "
                              "whose additionalFeatures columns are dropped",
                              None)
@@ -184,6 +247,44 @@ class _VWParams(Params):
                 numBits=self.get("numBits")).transform(df)
             extra.append(out)
         return df, extra
+
+    def _fused_plan(self, df: pd.DataFrame):
+        """(feature columns, [(a, b) column numbers], pair seeds) when
+        fusedInteractions can serve this configuration, else None (the
+        materialised path).  Pair p takes the seed of the column
+        __interact_p that _feature_frame would have added."""
+        if not self.get("fusedInteractions") or self.get("bfgs"):
+            return None
+        from .murmur import hash_string
+        ig = self.get("ignoreNamespaces") or []
+        cols = [self.get("featuresCol")] + [
+            c for c in (self.get("additionalFeatures") or [])
+            if c[:1] not in ig]
+        specs = list(self.get("interactions") or [])
+        specs += self._resolve_quadratic(df)
+        if len(specs) > backend.VW_INTERACT_MAX_PAIRS:
+            return None
+        pairs = []
+        for spec in specs:
+            names = (list(spec) if isinstance(spec, (list, tuple))
+                     else [c.strip() for c in str(spec).split(",")])
+            if len(names) != 2 or any(c not in cols for c in names):
+                return None
+            pairs.append([cols.index(names[0]), cols.index(names[1])])
+        seeds = [hash_string(f"__interact_{k}") & 0x3FFFFFFF
+                 for k in range(len(pairs))]
+        return cols, pairs, seeds
+
+    def _compact_batch(self, df: pd.DataFrame, plan, device):
+        """The plan's compact batch: (idx, val, ns_off) and the constant
+        kernel arguments (col_seed, pairs, pair_seed)."""
+        cols, pairs, seeds = plan
+        idx, val, ns_off, col_seed = _extract_compact(df, cols, device)
+        return (idx, val, ns_off), (
+            col_seed,
+            torch.tensor(pairs, dtype=torch.int32,
+                         device=device).reshape(-1, 2),
+            torch.tensor(seeds, dtype=torch.int32, device=device))
 
     def _parse_args(self):
         """Apply passThroughArgs (analog of the reference building the VW arg
@@ -304,12 +405,18 @@ class _VWBase(_VWParams, Estimator):
         comm = get_comm()
         device = default_device(self.get("device"))
         t_ingest = time.perf_counter()
-        df, extra_cols = self._feature_frame(df)
-        idx, val, off, _ = _extract_csr(df, self.get("featuresCol"),
-                                        extra_cols, device)
-        # VW semantics: every feature index lands in the 2^b table (hash &
-        # mask); the concatenated column offsets can exceed it otherwise
-        idx = idx & ((1 << self.get("numBits")) - 1)
+        plan = self._fused_plan(df)
+        if plan is not None:
+            # off is the compact batch's ns_off; the kernels seed, mask and
+            # cross its raw indices themselves
+            (idx, val, off), fused = self._compact_batch(df, plan, device)
+        else:
+            df, extra_cols = self._feature_frame(df)
+            idx, val, off, _ = _extract_csr(df, self.get("featuresCol"),
+                                            extra_cols, device)
+            # VW semantics: every feature index lands in the 2^b table (hash
+            # & mask); the concatenated column offsets can exceed it otherwise
+            idx = idx & ((1 << self.get("numBits")) - 1)
         y = df[self.get("labelCol")].to_numpy(dtype=np.float32)
         if self._binary_labels and getattr(self, "_convert_labels", True):
             y = np.where(y > 0, 1.0, -1.0).astype(np.float32)
@@ -365,10 +472,11 @@ class _VWBase(_VWParams, Estimator):
             period = max(2, self.get("holdoutPeriod"))
             pos = torch.arange(n, device=off.device)
             ho_mask = (pos % period) == (period - 1)
-            ti, tv, to = _filter_csr(idx, val, off, ~ho_mask)
+            filt = _filter_csr if plan is None else _filter_compact
+            ti, tv, to = filt(idx, val, off, ~ho_mask)
             tr = (ti, tv, to, labels[~ho_mask],
                   ex_w[~ho_mask] if ex_w is not None else None)
-            hi, hv, hoff = _filter_csr(idx, val, off, ho_mask)
+            hi, hv, hoff = filt(idx, val, off, ho_mask)
             ho = (hi, hv, hoff, labels[ho_mask])
         t_idx, t_val, t_off, t_y, t_w = tr
         n_train = int(t_y.numel())
@@ -379,6 +487,15 @@ class _VWBase(_VWParams, Estimator):
             t0 = time.perf_counter()
             for s in range(0, n_train, bs):
                 e = min(s + bs, n_train)
+                if plan is not None:
+                    first, last = int(t_off[s, 0]), int(t_off[e - 1, -1])
+                    backend.vw_sgd_minibatch_interact(
+                        t_idx[first:last], t_val[first:last],
+                        t_off[s:e] - first, *fused, bits, t_y[s:e], w, g, lr,
+                        l2, power_t, loss,
+                        t_w[s:e] if t_w is not None else None, s_tbl,
+                        invariant=self.get("invariant"))
+                    continue
                 o = t_off[s:e + 1] - t_off[s]
                 sl = slice(int(t_off[s]), int(t_off[e]))
                 backend.vw_sgd_minibatch(
@@ -401,8 +518,10 @@ class _VWBase(_VWParams, Estimator):
                 w.copy_(torch.sign(w) * (w.abs() - lr * l1).clamp_min(0))
             multipass_s += time.perf_counter() - t0
             if ho is not None:
-                hloss = _avg_loss(backend.vw_predict(ho[0], ho[1], ho[2], w),
-                                  ho[3], loss)
+                hp = (backend.vw_predict(ho[0], ho[1], ho[2], w)
+                      if plan is None else backend.vw_predict_interact(
+                          ho[0], ho[1], ho[2], *fused, bits, w))
+                hloss = _avg_loss(hp, ho[3], loss)
                 if comm.is_distributed:
                     t = torch.tensor([hloss, 1.0], device=w.device)
                     comm.all_reduce(t)
@@ -423,7 +542,7 @@ class _VWBase(_VWParams, Estimator):
                                     adaptive=g.cpu().numpy())
         for pname in ("labelCol", "featuresCol", "additionalFeatures",
                       "predictionCol", "numBits", "interactions",
-                      "ignoreNamespaces"):
+                      "fusedInteractions", "ignoreNamespaces"):
             model.set(pname, self.get(pname))
         model.set("lossFunction", loss)
         model._stats = pd.DataFrame([{
@@ -431,7 +550,7 @@ class _VWBase(_VWParams, Estimator):
             "ipassCurrent": (passes_run if n_passes else
                              self.get("numPasses")),
             "numberOfExamplesPerPass": n,
-            "totalNumberOfFeatures": int(off[-1]),
+            "totalNumberOfFeatures": int(off.reshape(-1)[-1]) if n else 0,
             "nativeIngestTimeNs": int(ingest_s * 1e9),
             "learnTimeNs": int(learn_s * 1e9),
             "multipassTimeNs": int(multipass_s * 1e9),
@@ -471,10 +590,15 @@ class _VWModelBase(_VWParams, Model):
 
     def _raw(self, df: pd.DataFrame) -> np.ndarray:
         device = default_device(self.get("device"))
+        w = torch.from_numpy(self.weights).to(device)
+        plan = self._fused_plan(df)
+        if plan is not None:
+            batch, fused = self._compact_batch(df, plan, device)
+            return backend.vw_predict_interact(
+                *batch, *fused, w.numel().bit_length() - 1, w).cpu().numpy()
         df, extra_cols = self._feature_frame(df)
         idx, val, off, _ = _extract_csr(df, self.get("featuresCol"),
                                         extra_cols, device)
-        w = torch.from_numpy(self.weights).to(device)
         idx = idx & (w.numel() - 1)  # table mask, matching _fit
         return backend.vw_predict(idx, val, off, w).cpu().numpy()
 

@@ -129,3 +129,82 @@ def vw_sgd_minibatch(indices, values, offsets, labels, w_tbl, g_tbl, lr, l2,
         scale = normalized(scale)
     w_tbl.index_add_(0, il, -lr * g * scale)
     return preds
+
+
+# ------------------------------------------------ compact namespace batches
+FNV_PRIME = 16777619  # featurizer.FNV_PRIME
+_U32 = 0xFFFFFFFF
+_SEED_MASK = 0x3FFFFFFF
+
+
+def _ranges(starts, counts):
+    """Concatenation of arange(starts[k], starts[k] + counts[k]) and, for
+    each element, the k it came from."""
+    seg = torch.repeat_interleave(
+        torch.arange(counts.numel(), device=counts.device), counts)
+    first = counts.cumsum(0) - counts
+    within = torch.arange(seg.numel(), device=counts.device) - first[seg]
+    return starts[seg] + within, seg, within
+
+
+def expand_interact(indices, values, ns_off, col_seed, pairs, pair_seed,
+                    bits):
+    """Compact namespace batch -> flat CSR (indices int32, values float32,
+    offsets int64): the executable definition of the format the
+    vw_*_interact kernels read.
+
+    indices/values hold every column's raw entries once; ns_off (n_ex,
+    n_cols + 1) bounds column c of example ex as [ns_off[ex, c],
+    ns_off[ex, c + 1]).  An example's features are its linear entries column
+    by column, slot ((raw + col_seed[c]) & 0x3FFFFFFF) & M with M = 2^bits -
+    1, then for each pair (a, b) in turn every i of column a with every j of
+    column b (j fastest): h = ((raw_i * FNV_PRIME) ^ raw_j) & M in unsigned
+    32-bit arithmetic, slot ((h + pair_seed[p]) & 0x3FFFFFFF) & M, value the
+    float32 product x_i * x_j.  Features that share a slot are not merged."""
+    mask = (1 << bits) - 1
+    n_ex, n_cols = ns_off.shape[0], ns_off.shape[1] - 1
+    dev = indices.device
+    raw = indices.long() & _U32
+    cseed = col_seed.long() & _U32
+    pseed = pair_seed.long() & _U32
+    cnt = ns_off[:, 1:] - ns_off[:, :-1]
+    # linear entries: (example, column) ranges in row-major order
+    pos, seg, _ = _ranges(ns_off[:, :-1].reshape(-1), cnt.reshape(-1))
+    ex_parts = [seg // max(n_cols, 1)]
+    slot_parts = [(((raw[pos] + cseed[seg % max(n_cols, 1)]) & _U32)
+                   & _SEED_MASK) & mask]
+    val_parts = [values[pos]]
+    for p, (a, b) in enumerate(pairs.tolist()):
+        n_b = cnt[:, b]
+        _, ex, t = _ranges(torch.zeros(n_ex, dtype=torch.long, device=dev),
+                           cnt[:, a] * n_b)
+        i = t // n_b[ex].clamp_min(1)
+        j = t - i * n_b[ex]
+        pi, pj = ns_off[ex, a] + i, ns_off[ex, b] + j
+        h = (((raw[pi] * FNV_PRIME) & _U32) ^ raw[pj]) & mask
+        ex_parts.append(ex)
+        slot_parts.append((((h + pseed[p]) & _U32) & _SEED_MASK) & mask)
+        val_parts.append(values[pi] * values[pj])
+    ex_all = torch.cat(ex_parts)
+    order = torch.sort(ex_all, stable=True).indices
+    off = torch.zeros(n_ex + 1, dtype=torch.long, device=dev)
+    off[1:] = torch.bincount(ex_all, minlength=n_ex).cumsum(0)
+    return (torch.cat(slot_parts)[order].to(torch.int32),
+            torch.cat(val_parts)[order].to(torch.float32), off)
+
+
+def vw_sgd_minibatch_interact(indices, values, ns_off, col_seed, pairs,
+                              pair_seed, bits, labels, w_tbl, g_tbl, lr, l2,
+                              power_t, loss: str, ex_weight=None, s_tbl=None,
+                              invariant=False):
+    idx, val, off = expand_interact(indices, values, ns_off, col_seed, pairs,
+                                    pair_seed, bits)
+    return vw_sgd_minibatch(idx, val, off, labels, w_tbl, g_tbl, lr, l2,
+                            power_t, loss, ex_weight, s_tbl, invariant)
+
+
+def vw_predict_interact(indices, values, ns_off, col_seed, pairs, pair_seed,
+                        bits, w_tbl):
+    idx, val, off = expand_interact(indices, values, ns_off, col_seed, pairs,
+                                    pair_seed, bits)
+    return vw_predict(idx, val, off, w_tbl)

@@ -173,6 +173,47 @@ def vw_predict(indices, values, offsets, weights_tbl):
     return sgd_ref.vw_predict(indices, values, offsets, weights_tbl)
 
 
+VW_INTERACT_MAX_PAIRS = 16  # VWI_MAX_PAIRS of vw_interact_kernels.hip
+
+
+def vw_interact_window() -> int:
+    """Entries of one example that the interact kernels hold in LDS; longer
+    examples read the rest from global memory."""
+    return _require_ext().vw_interact_window()
+
+
+def vw_sgd_minibatch_interact(indices, values, ns_off, col_seed, pairs,
+                              pair_seed, bits, labels, weights_tbl,
+                              adaptive_tbl, lr, l2, power_t, loss: str,
+                              ex_weight=None, normalize_tbl=None,
+                              invariant=False):
+    """vw_sgd_minibatch over a compact namespace batch whose column pairs
+    are crossed inside the kernel (VW -q); the format is defined by
+    sgd_ref.expand_interact."""
+    if weights_tbl.is_cuda:
+        return _require_ext().vw_sgd_minibatch_interact(
+            indices, values, ns_off, col_seed, pairs, pair_seed, bits, labels,
+            weights_tbl, adaptive_tbl, lr, l2, power_t,
+            {"squared": 0, "logistic": 1, "hinge": 2}[loss], ex_weight,
+            normalize_tbl, invariant)
+    from ..models.vw import sgd_ref
+    return sgd_ref.vw_sgd_minibatch_interact(
+        indices, values, ns_off, col_seed, pairs, pair_seed, bits, labels,
+        weights_tbl, adaptive_tbl, lr, l2, power_t, loss, ex_weight,
+        normalize_tbl, invariant)
+
+
+def vw_predict_interact(indices, values, ns_off, col_seed, pairs, pair_seed,
+                        bits, weights_tbl):
+    if weights_tbl.is_cuda:
+        return _require_ext().vw_predict_interact(
+            indices, values, ns_off, col_seed, pairs, pair_seed, bits,
+            weights_tbl)
+    from ..models.vw import sgd_ref
+    return sgd_ref.vw_predict_interact(indices, values, ns_off, col_seed,
+                                       pairs, pair_seed, bits, weights_tbl)
+
+
 # --------------------------------------------------------------- sparse CSR
 def csr_hist_fixed(indptr, col, binv, gq, hq, rows, nf, n_bins):
     """Fixed-point histogram over STORED entries of `rows` from a binned CSR

@@ -45,6 +45,16 @@ void launch_vw_sgd(const int*, const float*, const long*, const float*,
                    int, int, long, float*, hipStream_t);
 void launch_vw_predict(const int*, const float*, const long*, const float*,
                        long, float*, hipStream_t);
+int vw_interact_window();
+int vw_interact_max_pairs();
+int launch_vw_sgd_interact(const int*, const float*, const long*, const int*,
+                           int, const int*, const int*, int, int,
+                           const float*, const float*, float*, float*, float*,
+                           float, float, float, int, int, long, float*,
+                           hipStream_t);
+int launch_vw_predict_interact(const int*, const float*, const long*,
+                               const int*, int, const int*, const int*, int,
+                               int, const float*, long, float*, hipStream_t);
 void launch_tree_shap(const int*, const float*, const int*, const int*,
                       const float*, const float*, const long*, const int*,
                       const unsigned*, const float*, long, int, int, int, int,
@@ -429,6 +439,107 @@ torch::Tensor vw_predict(torch::Tensor idx, torch::Tensor val,
   launch_vw_predict(idx.data_ptr<int>(), val.data_ptr<float>(),
                     off.data_ptr<long>(), w_tbl.data_ptr<float>(), n_ex,
                     out.data_ptr<float>(), cur_stream());
+  return out;
+}
+
+// vw_interact_kernels.hip: the compact namespace batch.  idx/val hold each
+// column's raw entries once; ns_off (n_ex, n_cols + 1) bounds them; pairs
+// (n_pairs, 2) names the columns to cross.  Returns n_ex, n_cols, n_pairs.
+static std::tuple<long, int, int> check_vw_interact(
+    const torch::Tensor& idx, const torch::Tensor& val,
+    const torch::Tensor& ns_off, const torch::Tensor& col_seed,
+    const torch::Tensor& pairs, const torch::Tensor& pair_seed, long bits,
+    const torch::Tensor& w_tbl) {
+  CHECK_DEV(idx); CHECK_CONTIG(idx);
+  CHECK_DEV(val); CHECK_CONTIG(val);
+  CHECK_DEV(ns_off); CHECK_CONTIG(ns_off);
+  CHECK_DEV(col_seed); CHECK_CONTIG(col_seed);
+  CHECK_DEV(pairs); CHECK_CONTIG(pairs);
+  CHECK_DEV(pair_seed); CHECK_CONTIG(pair_seed);
+  CHECK_DEV(w_tbl); CHECK_CONTIG(w_tbl);
+  TORCH_CHECK(idx.dtype() == torch::kInt32 && val.dtype() == torch::kFloat32
+              && idx.dim() == 1 && idx.numel() == val.numel(),
+              "idx int32 and val float32 of one length");
+  TORCH_CHECK(col_seed.dtype() == torch::kInt32 && col_seed.dim() == 1,
+              "col_seed must be int32 (n_cols)");
+  const long n_cols = col_seed.numel();
+  TORCH_CHECK(ns_off.dtype() == torch::kInt64 && ns_off.dim() == 2
+              && ns_off.size(1) == n_cols + 1,
+              "ns_off must be int64 (n_ex, n_cols + 1)");
+  TORCH_CHECK(pairs.dtype() == torch::kInt32 && pairs.dim() == 2
+              && pairs.size(1) == 2, "pairs must be int32 (n_pairs, 2)");
+  TORCH_CHECK(pair_seed.dtype() == torch::kInt32 && pair_seed.dim() == 1
+              && pair_seed.numel() == pairs.size(0),
+              "pair_seed must be int32 (n_pairs)");
+  TORCH_CHECK(pairs.size(0) <= vw_interact_max_pairs(), "at most ",
+              vw_interact_max_pairs(), " pairs");
+  TORCH_CHECK(n_cols < (1L << 20), "too many columns");
+  TORCH_CHECK(bits >= 1 && bits <= 30, "bits must be in [1, 30]");
+  TORCH_CHECK(w_tbl.dtype() == torch::kFloat32
+              && w_tbl.numel() >= (1L << bits),
+              "the weight table must hold 2^bits float32");
+  return {ns_off.size(0), (int)n_cols, (int)pairs.size(0)};
+}
+
+torch::Tensor vw_sgd_minibatch_interact(
+    torch::Tensor idx, torch::Tensor val, torch::Tensor ns_off,
+    torch::Tensor col_seed, torch::Tensor pairs, torch::Tensor pair_seed,
+    long bits, torch::Tensor label, torch::Tensor w_tbl, torch::Tensor g_tbl,
+    double lr, double l2, double power_t, long loss,
+    c10::optional<torch::Tensor> ex_weight,
+    c10::optional<torch::Tensor> s_tbl, bool invariant) {
+  auto [n_ex, n_cols, n_pairs] = check_vw_interact(
+      idx, val, ns_off, col_seed, pairs, pair_seed, bits, w_tbl);
+  CHECK_DEV(g_tbl); CHECK_CONTIG(g_tbl);
+  CHECK_DEV(label); CHECK_CONTIG(label);
+  TORCH_CHECK(g_tbl.dtype() == torch::kFloat32
+              && g_tbl.numel() == w_tbl.numel(), "g_tbl must match w_tbl");
+  TORCH_CHECK(label.dtype() == torch::kFloat32 && label.numel() == n_ex,
+              "one float32 label per example");
+  TORCH_CHECK(loss >= 0 && loss <= 2, "loss must be 0, 1 or 2");
+  const float* wptr = nullptr;
+  if (ex_weight.has_value()) {
+    CHECK_DEV((*ex_weight)); CHECK_CONTIG((*ex_weight));
+    TORCH_CHECK(ex_weight->dtype() == torch::kFloat32
+                && ex_weight->numel() == n_ex,
+                "one float32 importance weight per example");
+    wptr = ex_weight->data_ptr<float>();
+  }
+  float* sptr = nullptr;
+  if (s_tbl.has_value()) {
+    CHECK_DEV((*s_tbl)); CHECK_CONTIG((*s_tbl));
+    TORCH_CHECK(s_tbl->dtype() == torch::kFloat32
+                && s_tbl->numel() == w_tbl.numel(),
+                "s_tbl must match w_tbl");
+    sptr = s_tbl->data_ptr<float>();
+  }
+  auto preds = torch::zeros({n_ex}, w_tbl.options());
+  const int err = launch_vw_sgd_interact(
+      idx.data_ptr<int>(), val.data_ptr<float>(), ns_off.data_ptr<long>(),
+      col_seed.data_ptr<int>(), n_cols, pairs.data_ptr<int>(),
+      pair_seed.data_ptr<int>(), n_pairs, (int)bits, label.data_ptr<float>(),
+      wptr, w_tbl.data_ptr<float>(), g_tbl.data_ptr<float>(), sptr, (float)lr,
+      (float)l2, (float)power_t, (int)loss, invariant ? 1 : 0, n_ex,
+      preds.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(err == 0, "vw_sgd_interact launch failed: ",
+              err < 0 ? "too many pairs" : hipGetErrorString((hipError_t)err));
+  return preds;
+}
+
+torch::Tensor vw_predict_interact(
+    torch::Tensor idx, torch::Tensor val, torch::Tensor ns_off,
+    torch::Tensor col_seed, torch::Tensor pairs, torch::Tensor pair_seed,
+    long bits, torch::Tensor w_tbl) {
+  auto [n_ex, n_cols, n_pairs] = check_vw_interact(
+      idx, val, ns_off, col_seed, pairs, pair_seed, bits, w_tbl);
+  auto out = torch::zeros({n_ex}, w_tbl.options());
+  const int err = launch_vw_predict_interact(
+      idx.data_ptr<int>(), val.data_ptr<float>(), ns_off.data_ptr<long>(),
+      col_seed.data_ptr<int>(), n_cols, pairs.data_ptr<int>(),
+      pair_seed.data_ptr<int>(), n_pairs, (int)bits, w_tbl.data_ptr<float>(),
+      n_ex, out.data_ptr<float>(), cur_stream());
+  TORCH_CHECK(err == 0, "vw_predict_interact launch failed: ",
+              err < 0 ? "too many pairs" : hipGetErrorString((hipError_t)err));
   return out;
 }
 
@@ -1368,6 +1479,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "stable ordered row partition, single sync");
   m.def("vw_sgd_minibatch", &vw_sgd_minibatch, "adaptive sparse SGD minibatch");
   m.def("vw_predict", &vw_predict, "sparse linear predict");
+  m.def("vw_sgd_minibatch_interact", &vw_sgd_minibatch_interact,
+        "adaptive sparse SGD minibatch, namespace pairs crossed in-kernel");
+  m.def("vw_predict_interact", &vw_predict_interact,
+        "sparse linear predict, namespace pairs crossed in-kernel");
+  m.def("vw_interact_window", &vw_interact_window,
+        "entries of one example held in LDS by the interact kernels");
+  m.def("vw_interact_max_pairs", &vw_interact_max_pairs,
+        "most namespace pairs one interact launch takes");
   m.def("tree_shap", &tree_shap, "path-dependent TreeSHAP contributions");
   m.def("tree_shap_csr", &tree_shap_csr,
         "TreeSHAP over CSR rows, compact per-used-feature contributions");
