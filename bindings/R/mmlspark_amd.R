@@ -795,7 +795,7 @@ ml_index_to_value <- function(inputCol = NULL, outputCol = NULL, levels = NULL) 
   stage
 }
 
-ml_isolation_forest <- function(featuresCol = NULL, featureCols = NULL, predictionCol = NULL, scoreCol = NULL, numEstimators = NULL, maxSamples = NULL, maxFeatures = NULL, bootstrap = NULL, contamination = NULL, randomSeed = NULL) {
+ml_isolation_forest <- function(featuresCol = NULL, featureCols = NULL, predictionCol = NULL, scoreCol = NULL, numEstimators = NULL, maxSamples = NULL, maxFeatures = NULL, bootstrap = NULL, contamination = NULL, randomSeed = NULL, fusedBuild = NULL) {
   stage <- mmlspark_amd$models$iforest$IsolationForest()
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
   if (!is.null(featureCols)) stage$set("featureCols", featureCols)
@@ -807,6 +807,7 @@ ml_isolation_forest <- function(featuresCol = NULL, featureCols = NULL, predicti
   if (!is.null(bootstrap)) stage$set("bootstrap", bootstrap)
   if (!is.null(contamination)) stage$set("contamination", contamination)
   if (!is.null(randomSeed)) stage$set("randomSeed", randomSeed)
+  if (!is.null(fusedBuild)) stage$set("fusedBuild", fusedBuild)
   stage
 }
 

@@ -3,7 +3,12 @@ LinkedIn's Scala isolation-forest: core/.../isolationforest/IsolationForest.scal
 here the subsampled random-tree build and path-length scoring are ours).
 
 Scoring is array-based tree traversal (torch, CPU/GPU-generic); the anomaly
-score is 2^(-E[h(x)]/c(n)) with the standard average-path normalizer."""
+score is 2^(-E[h(x)]/c(n)) with the standard average-path normalizer.
+
+fusedBuild=True grows the forest of ops/cpu_ref.py::iforest_build instead:
+stateless counter-based draws, on a GPU one HIP block per tree
+(ops/hip/iforest_kernels.hip), the same model for a seed on CPU and GPU;
+MMLSPARK_AMD_IFOREST_FUSED=0 keeps that path on the numpy definition."""
 from __future__ import annotations
 
 import math
@@ -88,16 +93,62 @@ class IsolationForest(Estimator):
     contamination = Param("contamination", "expected outlier fraction (0 = "
                           "use score threshold 0.5)", 0.0, toFloat)
     randomSeed = Param("randomSeed", "seed", 1, toInt)
+    fusedBuild = Param("fusedBuild", "grow the forest from stateless "
+                       "counter-based draws, on a GPU one HIP block per tree "
+                       "(same seed, same model on CPU and GPU; differs from "
+                       "the default builder's forest)", False, toBool)
+
+    def _fit_fused(self, X: np.ndarray, sub_n: int, n_feat: int):
+        """The forest of ops/cpu_ref.py::iforest_build, grown by
+        iforest_build_k on a GPU; None when the fused path does not serve the
+        input (sub_n beyond one block's LDS, or non-finite features).  Unlike
+        _build_tree it never leaves a child empty."""
+        from ..ops import backend
+        if not 2 <= sub_n <= backend.IFOREST_MAX_SUB:
+            return None
+        device = default_device("auto")
+        Xt = torch.from_numpy(np.ascontiguousarray(X, np.float32)).to(device)
+        if not bool(torch.isfinite(Xt).all()):
+            return None
+        out = backend.iforest_build(Xt, self.get("numEstimators"), sub_n,
+                                    n_feat, self.get("bootstrap"),
+                                    self.get("randomSeed"))
+        _, feat, thr, lft, rgt, size, depth, offs = (
+            t.cpu().numpy() for t in out)
+        sizes = np.unique(size)            # c(size) once per distinct size
+        c = np.array([_avg_path(max(float(s), 1.0)) for s in sizes])
+        leaf_value = np.where(feat < 0, depth + c[np.searchsorted(sizes, size)],
+                              0.0).astype(np.float32)
+        model = IsolationForestModel()
+        model.set("forestArrays", {
+            "feature": feat, "threshold": thr, "left": lft, "right": rgt,
+            "size": size.astype(np.float32), "offsets": offs,
+            "sub_n": np.asarray([sub_n], np.int64),
+            "leaf_value": leaf_value,
+        })
+        return model, Xt
 
     def _fit(self, df: pd.DataFrame):
         X = features_matrix(df, self.get("featuresCol"), self.get("featureCols"))
-        rng = np.random.default_rng(self.get("randomSeed"))
         n, nf = X.shape
         ms = self.get("maxSamples")
         sub_n = int(ms if ms > 1 else max(2, ms * n))
         sub_n = min(sub_n, n)
-        height = math.ceil(math.log2(max(sub_n, 2)))
         n_feat = max(1, int(self.get("maxFeatures") * nf))
+        fused = self._fit_fused(X, sub_n, n_feat) \
+            if self.get("fusedBuild") else None
+        if fused is not None:
+            model, Xt = fused
+            for p in ("featuresCol", "featureCols", "predictionCol",
+                      "scoreCol"):
+                model.set(p, self.get(p))
+            if self.get("contamination") > 0:   # X is already on the device
+                scores = model._scores_tensor(Xt)
+                model.set("scoreThreshold", float(np.quantile(
+                    scores, 1 - self.get("contamination"))))
+            return model
+        rng = np.random.default_rng(self.get("randomSeed"))
+        height = math.ceil(math.log2(max(sub_n, 2)))
         trees = []
         for _ in range(self.get("numEstimators")):
             rows = (rng.integers(0, n, size=sub_n) if self.get("bootstrap")
@@ -168,16 +219,21 @@ class IsolationForestModel(Model):
         return val
 
     def _scores(self, X: np.ndarray) -> np.ndarray:
+        device = default_device("auto")
+        return self._scores_tensor(
+            torch.from_numpy(np.ascontiguousarray(X)).to(device))
+
+    def _scores_tensor(self, Xt: torch.Tensor) -> np.ndarray:
+        """Scores of rows already on the scoring device."""
         from ..ops import backend
         f = self.get("forestArrays")
         if "leaf_value" not in f:
             f = dict(f)
             f["leaf_value"] = self._leaf_depth_values(f)
             self.set("forestArrays", f)
-        device = default_device("auto")
+        device = Xt.device
         sub_n = int(f["sub_n"][0])
         n_trees = len(f["offsets"]) - 1
-        Xt = torch.from_numpy(np.ascontiguousarray(X)).to(device)
         dev = lambda a, dt: torch.from_numpy(  # noqa: E731
             np.ascontiguousarray(a)).to(device).to(dt)
         # shift thresholds so the kernel's `x <= thr` matches iforest's

@@ -1228,3 +1228,57 @@ def masked_image_batch(image, segments, states, fill, size, lut, m=None):
     return cpu_ref.masked_image_batch(image.cpu(), segments.cpu(),
                                       states.cpu(), m, fill, size,
                                       lut.cpu()).to(dev)
+
+
+# -------------------------------------------------------- isolation forest
+IFOREST_MAX_SUB = cpu_ref.IFOREST_MAX_SUB   # one tree's subsample in one block's LDS
+
+
+def _iforest_fused(t) -> bool:
+    """GPU tensors go to iforest_kernels.hip unless
+    MMLSPARK_AMD_IFOREST_FUSED=0."""
+    import os
+    return t.is_cuda and os.environ.get(
+        "MMLSPARK_AMD_IFOREST_FUSED", "1") != "0"
+
+
+def check_iforest_inputs(X, n_trees, sub_n, n_feat):
+    """Everything iforest_build indexes with, checked in O(1); raises
+    ValueError and nothing is launched."""
+    def bad(msg):
+        raise ValueError("iforest_build: " + msg)
+
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.float32:
+        bad("X must be a float32 tensor")
+    if X.dim() != 2 or X.shape[1] < 1:
+        bad("X must be (n, nf) with nf >= 1")
+    if not X.is_contiguous():
+        bad("X must be contiguous")
+    n, nf = X.shape
+    if n >= (1 << 31):
+        bad("X must have fewer than 2^31 rows")
+    if int(n_trees) < 1:
+        bad("n_trees must be at least 1")
+    if not 2 <= int(sub_n) <= min(n, IFOREST_MAX_SUB):
+        bad("sub_n must be in [2, min(n, %d)]" % IFOREST_MAX_SUB)
+    if not 1 <= int(n_feat) <= nf:
+        bad("n_feat must be in [1, nf]")
+
+
+def iforest_build(X, n_trees, sub_n, n_feat, bootstrap=False, seed=1):
+    """Grow n_trees isolation trees of sub_n sampled rows each over finite
+    X (n, nf) float32, as cpu_ref.iforest_build defines them: the result
+    depends on the arguments alone, not on the device.  On the GPU one block
+    builds one tree (iforest_build_k) and the host loops over nothing.
+    Returns (sample_rows (n_trees, sub_n) int32, feature, threshold, left,
+    right, size, depth, offsets int64) on X's device."""
+    check_iforest_inputs(X, n_trees, sub_n, n_feat)
+    seed = int(seed) & (2 ** 64 - 1)
+    if _iforest_fused(X):
+        signed = seed - 2 ** 64 if seed >= 2 ** 63 else seed
+        return tuple(_require_ext().iforest_build(
+            X, int(n_trees), int(sub_n), int(n_feat), bool(bootstrap),
+            signed))
+    out = cpu_ref.iforest_build(X.cpu(), int(n_trees), int(sub_n),
+                                int(n_feat), bool(bootstrap), seed)
+    return tuple(t.to(X.device) for t in out)

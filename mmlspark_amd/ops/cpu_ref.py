@@ -1111,3 +1111,184 @@ def masked_image_batch(image, segments, states, m, fill, size, lut):
         batch = torch.nn.functional.interpolate(
             batch, size=(size, size), mode="bilinear", align_corners=False)
     return batch
+
+
+# -------------------------------------------------------- isolation forest
+# The definition of the fused isolation-forest build; ops/hip/
+# iforest_kernels.hip reproduces it bit for bit.
+IFOREST_MAX_SUB = 4096
+IFOREST_RETRIES = 8
+_IF_GOLD = 0x9E3779B97F4A7C15
+_IF_ROWPERM, _IF_BOOT, _IF_FEATPERM, _IF_NODE_FEAT, _IF_NODE_THR = range(5)
+
+
+def _if_fin(z):
+    """splitmix64's finaliser on uint64 arrays (wrapping arithmetic)."""
+    import numpy as np
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def iforest_mix(seed, tree, purpose, path, draw):
+    """h = mix(seed, tree, purpose, path, draw), uint64: the seed plus the
+    golden-ratio constant goes through the finaliser, then every further
+    field is folded in as h = fin((h ^ field) + gold)."""
+    import numpy as np
+    gold = np.uint64(_IF_GOLD)
+    with np.errstate(over="ignore"):
+        h = _if_fin(np.asarray([seed & (2 ** 64 - 1)], np.uint64) + gold)
+        for field in (tree, purpose, path, draw):
+            h = _if_fin((h ^ np.asarray(field).astype(np.uint64)) + gold)
+    return h
+
+
+def _if_below(h, m):
+    """Index below m < 2^31: the high 32 bits of (h >> 32) * m."""
+    import numpy as np
+    return (((h >> np.uint64(32)) * np.uint64(m)) >> np.uint64(32)).astype(
+        np.int64)
+
+
+def iforest_half_bits(n):
+    """Half the width of the smallest even-bit power-of-two domain >= n."""
+    return (max(2, (int(n) - 1).bit_length()) + 1) // 2
+
+
+def _if_perm(seed, tree, purpose, x, n):
+    """Keyed 4-round Feistel bijection on 2^(2 * half) values, cycle-walked
+    from x < n until it lands below n again: a bijection on [0, n)."""
+    import numpy as np
+    half = np.uint64(iforest_half_bits(n))
+    mask = np.uint64((1 << int(half)) - 1)
+    tree = np.broadcast_to(np.asarray(tree), np.shape(x))
+    y = np.array(x, dtype=np.uint64)
+    todo = np.ones(y.shape, dtype=bool)
+    while todo.any():
+        v, t = y[todo], tree[todo]
+        L, R = v >> half, v & mask
+        for r in range(4):
+            F = (iforest_mix(seed, t, purpose, r, R) >> np.uint64(32)) & mask
+            L, R = R, L ^ F
+        y[todo] = (L << half) | R
+        todo = y >= np.uint64(n)
+    return y.astype(np.int64)
+
+
+def iforest_build(X, n_trees, sub_n, n_feat, bootstrap, seed):
+    """Grow n_trees isolation trees over X (n, nf) float32 from stateless,
+    counter-based draws, every level of the whole forest at once.
+
+    Sample slot s of tree t is row perm_t(s) (a Feistel bijection of [0, n),
+    so no duplicates), or with bootstrap an independent index draw.  A node
+    is named by its heap path (root 1, children 2p and 2p + 1) and all its
+    draws are keyed by it.  A node of size <= 1 or at depth
+    ceil(log2(max(sub_n, 2))) is a leaf; any other makes up to
+    IFOREST_RETRIES candidate draws of a feature (through featperm_t when
+    n_feat < nf) and splits on the first with hi > lo over its rows, at
+    thr = lo + u * (hi - lo) in float32, clamped into (lo, hi]; rows with
+    x < thr go left, so both children are non-empty (the host builder of
+    models/iforest.py can leave one empty).  With all candidates constant the
+    node is a leaf.
+
+    Returns (sample_rows (n_trees, sub_n) int32, feature, threshold, left,
+    right, size, depth, offsets int64): the compact forest
+    IsolationForestModel reads, nodes of a tree in level order, left to
+    right, left/right tree-local, feature -1 at leaves."""
+    import numpy as np
+    Xn = X.numpy()
+    n, nf = Xn.shape
+    height = int(np.ceil(np.log2(max(sub_n, 2))))
+    cap = 2 * sub_n - 1
+    trees = np.arange(n_trees, dtype=np.int64)
+    slots = np.arange(sub_n, dtype=np.int64)
+    tt = np.repeat(trees, sub_n)
+    ss = np.tile(slots, n_trees)
+    if bootstrap:
+        rows = _if_below(iforest_mix(seed, tt, _IF_BOOT, 0, ss), n)
+    else:
+        rows = _if_perm(seed, tt, _IF_ROWPERM, ss, n)
+    sample_rows = rows.reshape(n_trees, sub_n).astype(np.int32)
+
+    feature = np.full((n_trees, cap), -1, np.int32)
+    threshold = np.zeros((n_trees, cap), np.float32)
+    left = np.full((n_trees, cap), -1, np.int32)
+    right = np.full((n_trees, cap), -1, np.int32)
+    size = np.zeros((n_trees, cap), np.int32)
+    depth = np.zeros((n_trees, cap), np.int32)
+    count = np.ones(n_trees, np.int64)
+
+    # the active table of the level: one entry per node that tries to split,
+    # tree-major and left to right; ids holds their segments back to back
+    ids = rows
+    t_tree, t_len = trees, np.full(n_trees, sub_n, np.int64)
+    t_path = np.ones(n_trees, np.int64)
+    t_out = np.zeros(n_trees, np.int64)
+    d = 0
+    while len(t_tree):
+        m = len(t_tree)
+        starts = np.cumsum(t_len) - t_len
+        node = np.repeat(np.arange(m), t_len)
+        feat = np.full(m, -1, np.int64)
+        win = np.full(m, -1, np.int64)
+        lo, hi = np.zeros(m, np.float32), np.zeros(m, np.float32)
+        for draw in range(IFOREST_RETRIES):
+            un = win < 0
+            if not un.any():
+                break
+            f = _if_below(iforest_mix(seed, t_tree, _IF_NODE_FEAT, t_path,
+                                      draw), n_feat)
+            if n_feat < nf:
+                f = _if_perm(seed, t_tree, _IF_FEATPERM, f, nf)
+            v = Xn[ids, f[node]]
+            l, h = (np.minimum.reduceat(v, starts),
+                    np.maximum.reduceat(v, starts))
+            ok = un & (h > l)
+            feat[ok], win[ok], lo[ok], hi[ok] = f[ok], draw, l[ok], h[ok]
+        res = win >= 0
+        hmix = iforest_mix(seed, t_tree, _IF_NODE_THR, t_path,
+                           np.maximum(win, 0))
+        u = (hmix >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+        with np.errstate(over="ignore", invalid="ignore"):
+            thr = lo + u * (hi - lo)          # float32, one rounding per op
+        thr = np.where(thr < hi, thr, hi)
+        thr = np.where(thr > lo, thr, hi).astype(np.float32)
+        goes_left = res[node] & (Xn[ids, np.maximum(feat, 0)[node]]
+                                 < thr[node])
+        lcnt = np.add.reduceat(goes_left.astype(np.int64), starts)
+
+        # children get the next level-order numbers of their tree
+        rank = np.cumsum(res) - res
+        first = np.searchsorted(t_tree, t_tree)      # first entry of the tree
+        L = count[t_tree] + 2 * (rank - rank[first])
+        feature[t_tree, t_out] = np.where(res, feat, -1)
+        threshold[t_tree, t_out] = np.where(res, thr, 0)
+        left[t_tree, t_out] = np.where(res, L, -1)
+        right[t_tree, t_out] = np.where(res, L + 1, -1)
+        size[t_tree, t_out] = t_len
+        depth[t_tree, t_out] = d
+        count += 2 * np.bincount(t_tree[res], minlength=n_trees)
+
+        c_tree = np.repeat(t_tree[res], 2)
+        c_len = np.stack([lcnt[res], (t_len - lcnt)[res]], 1).reshape(-1)
+        c_path = np.stack([2 * t_path[res], 2 * t_path[res] + 1],
+                          1).reshape(-1)
+        c_out = np.stack([L[res], L[res] + 1], 1).reshape(-1)
+        size[c_tree, c_out] = c_len
+        depth[c_tree, c_out] = d + 1
+        active = (c_len > 1) & (d + 1 < height)
+        # stable partition of every split segment, then keep the positions
+        # whose child stays active
+        child = 2 * rank[node] + 1 - goes_left       # index into c_*
+        order = np.argsort(np.where(res[node], child, 2 * m), kind="stable")
+        order = order[:int(t_len[res].sum())]
+        ids = ids[order][active[child[order]]]
+        t_tree, t_len = c_tree[active], c_len[active]
+        t_path, t_out = c_path[active], c_out[active]
+        d += 1
+
+    offsets = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+    keep = np.arange(cap)[None, :] < count[:, None]
+    out = [sample_rows] + [a[keep] for a in (feature, threshold, left, right,
+                                             size, depth)] + [offsets]
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)) for a in out)

@@ -135,6 +135,14 @@ int launch_slic_segment(const unsigned char*, long, const long*, const long*,
 int launch_masked_image_batch(const unsigned char*, int, int, int, const int*,
                               const unsigned*, int, int, int, int, int,
                               const float*, float*, hipStream_t);
+int iforest_max_sub();
+int iforest_staged(int, int);
+int launch_iforest_build(const float*, long, int, int, int, int, int,
+                         unsigned long long, int*, int*, float*, int*, int*,
+                         int*, int*, int*, hipStream_t);
+int launch_iforest_compact(const int*, const float*, const int*, const int*,
+                           const int*, const int*, const long*, int, int,
+                           int*, float*, int*, int*, int*, int*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -1461,6 +1469,55 @@ torch::Tensor masked_image_batch(torch::Tensor img, torch::Tensor seg,
   return out;
 }
 
+// ---------------------------------------------------------- isolation forest
+// iforest_kernels.hip: one block grows one tree into a padded slab, a cumsum
+// over the node counts and one gather kernel make the compact forest.  The
+// only host wait is the read of the total node count that sizes the result.
+std::vector<torch::Tensor> iforest_build(torch::Tensor X, long n_trees,
+                                         long sub_n, long n_feat,
+                                         bool bootstrap, int64_t seed) {
+  CHECK_DEV(X); CHECK_CONTIG(X);
+  TORCH_CHECK(X.dtype() == torch::kFloat32 && X.dim() == 2,
+              "X must be (n, nf) float32");
+  const long n = X.size(0), nf = X.size(1);
+  TORCH_CHECK(n < (1L << 31) && nf >= 1 && nf < (1L << 24), "X too large");
+  TORCH_CHECK(sub_n >= 2 && sub_n <= iforest_max_sub() && sub_n <= n,
+              "sub_n out of range");
+  TORCH_CHECK(n_feat >= 1 && n_feat <= nf, "n_feat out of range");
+  TORCH_CHECK(n_trees >= 1 && n_trees < (1L << 20), "n_trees out of range");
+  const long cap = 2 * sub_n - 1;
+  const auto i32 = X.options().dtype(torch::kInt32);
+  auto rows = torch::empty({n_trees, sub_n}, i32);
+  auto slab_i = torch::empty({5, n_trees, cap}, i32);
+  auto slab_t = torch::empty({n_trees, cap}, X.options());
+  auto count = torch::empty({n_trees}, i32);
+  int* si = slab_i.data_ptr<int>();
+  const long plane = n_trees * cap;
+  int err = launch_iforest_build(
+      X.data_ptr<float>(), n, (int)nf, (int)n_trees, (int)sub_n, (int)n_feat,
+      bootstrap ? 1 : 0, (unsigned long long)seed, rows.data_ptr<int>(), si,
+      slab_t.data_ptr<float>(), si + plane, si + 2 * plane, si + 3 * plane,
+      si + 4 * plane, count.data_ptr<int>(), cur_stream());
+  TORCH_CHECK(err == 0, "iforest_build launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  auto offsets = torch::zeros({n_trees + 1}, X.options().dtype(torch::kInt64));
+  offsets.slice(0, 1).copy_(count.cumsum(0, torch::kInt64));
+  const long total = offsets[n_trees].item<int64_t>();
+  TORCH_CHECK(total >= n_trees && total <= plane, "iforest_build: bad counts");
+  auto out_i = torch::empty({5, total}, i32);
+  auto out_t = torch::empty({total}, X.options());
+  int* oi = out_i.data_ptr<int>();
+  err = launch_iforest_compact(
+      si, slab_t.data_ptr<float>(), si + plane, si + 2 * plane,
+      si + 3 * plane, si + 4 * plane, offsets.data_ptr<int64_t>(),
+      (int)n_trees, (int)cap, oi, out_t.data_ptr<float>(), oi + total,
+      oi + 2 * total, oi + 3 * total, oi + 4 * total, cur_stream());
+  TORCH_CHECK(err == 0, "iforest_compact launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return {rows, out_i[0], out_t, out_i[1], out_i[2], out_i[3], out_i[4],
+          offsets};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -1544,6 +1601,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grid-seeded centres of an H x W image at a cell size");
   m.def("masked_image_batch", &masked_image_batch,
         "masked samples of one image as the model's float32 NCHW batch");
+  m.def("iforest_build", &iforest_build,
+        "grow an isolation forest, one block per tree, compact level-order "
+        "arrays");
+  m.def("iforest_staged", &iforest_staged,
+        "1 when a tree's sample of sub_n x nf values is staged in LDS");
+  m.attr("IFOREST_MAX_SUB") = iforest_max_sub();
   m.attr("SLIC_MAX_K") = kSlicMaxK;
   m.attr("SLIC_MAX_DIM") = kSlicMaxDim;
   m.attr("ALS_MAX_K") = kAlsMaxK;
