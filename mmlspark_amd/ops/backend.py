@@ -62,17 +62,6 @@ def hist_build_fixed_pair(binned_pair, rows, grad, hess, n_bins, tail_bytes,
                                                 scale_g, scale_h)
 
 
-def hist_build_fixed(binned_i4, rows, grad, hess, n_bins, scale_g, scale_h):
-    """Fixed-point int64 histogram (GPU; 9x faster integer LDS atomics).
-    Returns (nf_pad, n_bins, 3) int64: [g*scale_g, h*scale_h, count]."""
-    if binned_i4.is_cuda:
-        return _require_ext().hist_build_fixed(binned_i4, rows, grad, hess,
-                                               n_bins, scale_g, scale_h)
-    h = cpu_ref.hist_build(binned_i4, rows, grad, hess, n_bins)
-    scale = torch.tensor([scale_g, scale_h, 1.0])
-    return (h.double() * scale).round().long()
-
-
 def partition_rows(binned_i4, rows, feature, threshold_bin, known_left=-1):
     if binned_i4.is_cuda:
         # ordered 3-kernel partition; ONE device→host sync, or zero when the
@@ -215,29 +204,12 @@ def vw_predict_interact(indices, values, ns_off, col_seed, pairs, pair_seed,
 
 
 # --------------------------------------------------------------- sparse CSR
-def csr_hist_fixed(indptr, col, binv, gq, hq, rows, nf, n_bins):
-    """Fixed-point histogram over STORED entries of `rows` from a binned CSR
-    shard; (nf, n_bins, 3) int64.  Implicit-zero correction is the caller's
-    (exact integer subtraction from leaf totals)."""
-    if binv.is_cuda:
-        return _require_ext().csr_hist_fixed(indptr, col, binv, gq, hq,
-                                             rows.contiguous(), nf, n_bins)
-    return cpu_ref.csr_hist_fixed(indptr, col, binv, gq, hq, rows, nf, n_bins)
-
-
-def csr_gather_bins(indptr, col, binv, rows, feature, zero_bin):
-    """Per-row bin of `feature` (missing → zero_bin) from a binned CSR shard."""
-    if binv.is_cuda:
-        return _require_ext().csr_gather_bins(indptr, col, binv,
-                                              rows.contiguous(), feature,
-                                              zero_bin).long()
-    return cpu_ref.csr_gather_bins(indptr, col, binv, rows, feature, zero_bin)
-
-
 def csr_hist_fixed_tot(indptr, col, binv, gq, hq, rows, nf, n_bins):
-    """Histogram over stored entries PLUS exact integer leaf totals
-    (sum gq, sum hq, count) in one launch — (hist, tot).  GPU: the
-    wave-cooperative v2 kernel; CPU: reference + torch sums."""
+    """Fixed-point histogram over STORED entries of `rows` from a binned CSR
+    shard, (nf, n_bins, 3) int64, PLUS exact integer leaf totals (sum gq,
+    sum hq, count) in one launch — (hist, tot).  Implicit-zero correction is
+    the caller's (exact integer subtraction from the totals).  GPU: the
+    wave-cooperative kernels; CPU: reference + torch sums."""
     if binv.is_cuda:
         return _require_ext().csr_hist_fixed_tot(indptr, col, binv, gq, hq,
                                                  rows.contiguous(), nf,

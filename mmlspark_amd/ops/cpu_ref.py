@@ -32,6 +32,28 @@ def hist_build(binned_i4: torch.Tensor, rows: torch.Tensor, grad: torch.Tensor,
     return hist
 
 
+def hist_build_fixed(binned_i4: torch.Tensor, rows: torch.Tensor,
+                     grad: torch.Tensor, hess: torch.Tensor, n_bins: int,
+                     scale_g: float, scale_h: float) -> torch.Tensor:
+    """Exact fixed-point histogram: what hist_build_fixed_pair_k sums, bit for
+    bit.  Per row gq = round(double(grad) * scale_g), hq likewise
+    (torch.round rounds half to even, like the kernel's llrint); int64 sums
+    have no order dependence.  binned_i4 as in hist_build.
+    returns: (ngroups*4, n_bins, 3) int64 [sum_gq, sum_hq, count].
+    """
+    nf = binned_i4.shape[0] * 4
+    r = rows.long()
+    m = r.numel()
+    b = binned_i4[:, r, :].permute(0, 2, 1).reshape(nf, m).long()
+    flat = (b + torch.arange(nf, device=b.device).unsqueeze(1) * n_bins)
+    gq = torch.round(grad[r].double() * scale_g).long()
+    hq = torch.round(hess[r].double() * scale_h).long()
+    src = torch.stack([gq, hq, torch.ones_like(gq)], dim=1)
+    hist = torch.zeros(nf * n_bins, 3, dtype=torch.int64, device=b.device)
+    hist.index_add_(0, flat.reshape(-1), src.repeat(nf, 1))
+    return hist.view(nf, n_bins, 3)
+
+
 def partition_rows(binned_i4: torch.Tensor, rows: torch.Tensor, feature: int,
                    threshold_bin: int):
     """Split rows into (left, right): left ⇔ bin[feature] <= threshold_bin."""
@@ -415,7 +437,8 @@ def _expand_csr(indptr: torch.Tensor, rows: torch.Tensor):
 def csr_hist_fixed(indptr, col, binv, gq, hq, rows, nf, n_bins):
     """Fixed-point histogram over stored CSR entries of `rows`
     (implicit zeros are corrected by the caller from exact leaf totals).
-    Returns (nf, n_bins, 3) int64 — matches csr_hist_fixed_k."""
+    Returns (nf, n_bins, 3) int64 — matches the histogram of
+    backend.csr_hist_fixed_tot."""
     e, rpos = _expand_csr(indptr, rows)
     hist = torch.zeros(nf * n_bins, 3, dtype=torch.int64, device=binv.device)
     if e.numel():
@@ -427,8 +450,8 @@ def csr_hist_fixed(indptr, col, binv, gq, hq, rows, nf, n_bins):
 
 
 def csr_gather_bins(indptr, col, binv, rows, feature: int, zero_bin: int):
-    """Bin of `feature` for each row (missing → zero_bin); matches
-    csr_gather_bin_k."""
+    """Bin of `feature` for each row (missing → zero_bin); matches the
+    device lookup csr_bin_of."""
     e, rpos = _expand_csr(indptr, rows)
     out = torch.full((rows.numel(),), int(zero_bin), dtype=torch.int64,
                      device=binv.device)

@@ -29,13 +29,9 @@ void launch_predict_leaf_csr(const int*, const float*, const int*, const int*,
                              const unsigned*, hipStream_t);
 void launch_bin_matrix(const float*, const float*, long, int, int, int, void*,
                        hipStream_t);
-void launch_hist_build_fixed(const void*, long, const int*, long, const float*,
-                             const float*, long long*, int, int, double,
-                             double, hipStream_t);
 void launch_hist_build_fixed_pair(const void*, long, const int*, long,
-                                  const float*, const float*, const void*,
-                                  long long*, int, int, int, double, double,
-                                  const int*, int, hipStream_t);
+                                  const float*, const float*, long long*, int,
+                                  int, int, double, double, hipStream_t);
 void launch_partition(const void*, long, const int*, long, int, int, int*,
                       int*, int*, hipStream_t);
 void launch_split_scan(const float*, int, long, int, float, float, float,
@@ -64,12 +60,6 @@ void launch_tree_shap_csr(const int*, const float*, const int*, const int*,
                           const int*, const unsigned*, const long*, const int*,
                           const float*, long, long, int, int, int, int, float*,
                           long, hipStream_t);
-void launch_csr_hist_fixed(const long*, const int*,
-                           const unsigned char*, const long long*,
-                           const long long*, const int*, long, long long*,
-                           int, hipStream_t);
-void launch_csr_gather_bin(const long*, const int*, const unsigned char*,
-                           const int*, long, int, int, int*, hipStream_t);
 void launch_csr_hist_fixed_v2(const long*, const int*, const unsigned char*,
                               const long long*, const long long*, const int*,
                               long, long long*, int, long long*, hipStream_t);
@@ -184,28 +174,9 @@ torch::Tensor hist_build_fixed_pair(torch::Tensor binned_pair,
   launch_hist_build_fixed_pair(binned_pair.data_ptr(), n_rows,
                                rows.data_ptr<int>(), rows.numel(),
                                grad.data_ptr<float>(), hess.data_ptr<float>(),
-                               nullptr,
                                (long long*)hist.data_ptr<int64_t>(),
                                (int)n_bins, (int)npairs, (int)tail_bytes,
-                               scale_g, scale_h, nullptr, -1, cur_stream());
-  return hist;
-}
-
-torch::Tensor hist_build_fixed(torch::Tensor binned_i4, torch::Tensor rows,
-                               torch::Tensor grad, torch::Tensor hess,
-                               long n_bins, double scale_g, double scale_h) {
-  CHECK_DEV(binned_i4); CHECK_CONTIG(binned_i4);
-  CHECK_DEV(rows); CHECK_CONTIG(rows);
-  TORCH_CHECK(rows.dtype() == torch::kInt32, "rows must be int32");
-  const long ngroups = binned_i4.size(0);
-  const long n_rows = binned_i4.size(1);
-  auto hist = torch::zeros({ngroups * 4, n_bins, 3},
-                           grad.options().dtype(torch::kInt64));
-  launch_hist_build_fixed(binned_i4.data_ptr(), n_rows, rows.data_ptr<int>(),
-                          rows.numel(), grad.data_ptr<float>(),
-                          hess.data_ptr<float>(),
-                          (long long*)hist.data_ptr<int64_t>(), (int)n_bins,
-                          (int)ngroups, scale_g, scale_h, cur_stream());
+                               scale_g, scale_h, cur_stream());
   return hist;
 }
 
@@ -619,34 +590,7 @@ torch::Tensor tree_shap_csr(torch::Tensor feat, torch::Tensor thr,
 }
 
 // --------------------------------------------------------------- sparse CSR
-torch::Tensor csr_hist_fixed(torch::Tensor indptr, torch::Tensor col,
-                             torch::Tensor binv, torch::Tensor gq,
-                             torch::Tensor hq, torch::Tensor rows,
-                             long nf, long n_bins) {
-  CHECK_DEV(indptr); CHECK_CONTIG(indptr);
-  CHECK_DEV(col); CHECK_CONTIG(col);
-  CHECK_DEV(binv); CHECK_CONTIG(binv);
-  CHECK_DEV(gq); CHECK_CONTIG(gq);
-  CHECK_DEV(hq); CHECK_CONTIG(hq);
-  CHECK_DEV(rows); CHECK_CONTIG(rows);
-  TORCH_CHECK(indptr.dtype() == torch::kInt64, "indptr must be int64");
-  TORCH_CHECK(col.dtype() == torch::kInt32, "col must be int32");
-  TORCH_CHECK(binv.dtype() == torch::kUInt8, "binv must be uint8");
-  TORCH_CHECK(gq.dtype() == torch::kInt64 && hq.dtype() == torch::kInt64,
-              "gq/hq must be int64 fixed point");
-  auto hist = torch::zeros({nf, n_bins, 3},
-                           gq.options().dtype(torch::kInt64));
-  launch_csr_hist_fixed(indptr.data_ptr<long>(), col.data_ptr<int>(),
-                        binv.data_ptr<unsigned char>(),
-                        (const long long*)gq.data_ptr<int64_t>(),
-                        (const long long*)hq.data_ptr<int64_t>(),
-                        rows.data_ptr<int>(), rows.numel(),
-                        (long long*)hist.data_ptr<int64_t>(), (int)n_bins,
-                        cur_stream());
-  return hist;
-}
-
-// v2: wave-cooperative row chunks + in-kernel leaf totals
+// wave-cooperative row chunks + in-kernel leaf totals
 std::tuple<torch::Tensor, torch::Tensor> csr_hist_fixed_tot(
     torch::Tensor indptr, torch::Tensor col, torch::Tensor binv,
     torch::Tensor gq, torch::Tensor hq, torch::Tensor rows, long nf,
@@ -684,22 +628,6 @@ std::tuple<torch::Tensor, torch::Tensor> csr_hist_fixed_tot(
                              cur_stream());
   }
   return {hist, tot};
-}
-
-torch::Tensor csr_gather_bins(torch::Tensor indptr, torch::Tensor col,
-                              torch::Tensor binv, torch::Tensor rows,
-                              long feature, long zero_bin) {
-  CHECK_DEV(indptr); CHECK_CONTIG(indptr);
-  CHECK_DEV(col); CHECK_CONTIG(col);
-  CHECK_DEV(binv); CHECK_CONTIG(binv);
-  CHECK_DEV(rows); CHECK_CONTIG(rows);
-  auto out = torch::empty({rows.numel()},
-                          rows.options().dtype(torch::kInt32));
-  launch_csr_gather_bin(indptr.data_ptr<long>(), col.data_ptr<int>(),
-                        binv.data_ptr<unsigned char>(), rows.data_ptr<int>(),
-                        rows.numel(), (int)feature, (int)zero_bin,
-                        out.data_ptr<int>(), cur_stream());
-  return out;
 }
 
 std::tuple<torch::Tensor, torch::Tensor> csr_partition_rows(
@@ -1522,8 +1450,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
         "fixed-point histogram over paired (8-feature) planes");
-  m.def("hist_build_fixed", &hist_build_fixed,
-        "fixed-point u64 histogram (fast LDS integer atomics)");
   m.def("predict_forest", &predict_forest, "GBDT ensemble raw scores");
   m.def("predict_leaf", &predict_leaf, "GBDT per-tree leaf indices");
   m.def("predict_forest_csr", &predict_forest_csr,
@@ -1547,10 +1473,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tree_shap", &tree_shap, "path-dependent TreeSHAP contributions");
   m.def("tree_shap_csr", &tree_shap_csr,
         "TreeSHAP over CSR rows, compact per-used-feature contributions");
-  m.def("csr_hist_fixed", &csr_hist_fixed,
-        "fixed-point histogram over stored CSR entries");
-  m.def("csr_gather_bins", &csr_gather_bins,
-        "per-row bin of one feature from CSR (missing -> zero bin)");
   m.def("csr_partition_rows", &csr_partition_rows,
         "fused CSR leaf partition (binary-search predicate, single sync)");
   m.def("csr_hist_fixed_tot", &csr_hist_fixed_tot,

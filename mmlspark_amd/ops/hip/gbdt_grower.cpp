@@ -8,7 +8,7 @@
 //    arena.  Every split scatters the parent's segment into the other buffer
 //    (stable left|right), so child histograms read CONTIGUOUS rows — the
 //    sparse row gather that bounded child hist builds (measured 2.3x,
-//    tools/hist_gather_probe.py) is gone; the cost is streaming ~124 B/row
+//    profiles/r01_hist_gather_probe.txt) is gone; the cost is ~124 B/row
 //    of arena payload per split, which HBM3E absorbs.  Live leaves always
 //    own disjoint row ranges, so two in-flight splits never overlap even
 //    across buffers.  When the root row set is every row in order (no

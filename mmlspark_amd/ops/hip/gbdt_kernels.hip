@@ -16,7 +16,6 @@
 //    near-coalesced.
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <cstdlib>
 
 #define WAVE 64
 #define DEV_INLINE __device__ __forceinline__
@@ -82,142 +81,19 @@ __global__ void hist_build_k(const uchar4* __restrict__ binned, long n_rows,
 // are chosen per iteration from max|g|, max h so per-chunk sums fit).
 // Bonus: integer histograms make multi-rank all_reduce and the sibling
 // subtraction trick bit-exact.
-template <int GPB>
-__global__ void hist_build_fixed_k(const uchar4* __restrict__ binned,
-                                   long n_rows, const int* __restrict__ rows,
-                                   long m, const float* __restrict__ grad,
-                                   const float* __restrict__ hess,
-                                   long long* __restrict__ hist, int n_bins,
-                                   int ngroups, long chunk, double scale_g,
-                                   double scale_h,
-                                   const int* __restrict__ nl_dev, int side) {
-  // side >= 0: child-of-partition mode — m is the PARENT row count (an
-  // upper bound for grid sizing) and the actual child range comes from the
-  // device-side left count nl_dev[0]: left = rows[0, nl), right = rows[nl,
-  // m).  Lets the distributed grower enqueue the smaller child's histogram
-  // without a host readback of the local partition count.
-  long base = 0, m_eff = m;
-  if (side >= 0) {
-    const long nl = nl_dev[0];
-    m_eff = (side == 0) ? nl : m - nl;
-    base = (side == 0) ? 0 : nl;
-  }
-  if ((long)blockIdx.x * chunk >= m_eff) return;  // surplus block: no work
-  rows += base;
-  extern __shared__ unsigned long long lds64[];  // [GPB*4][n_bins][2]
-  const int tid = threadIdx.x;
-  const int nfb = GPB * 4;
-  const int lds_elems = nfb * n_bins * 2;
-  for (int i = tid; i < lds_elems; i += blockDim.x) lds64[i] = 0ull;
-  __syncthreads();
-
-  const int gq0 = blockIdx.y * GPB;
-  const long start = (long)blockIdx.x * chunk;
-  const long end = min(start + chunk, m_eff);
-  constexpr unsigned long long CNT_ONE = 1ull << 44;
-
-  constexpr int ILP = 4;  // probe: +10% via deeper load batching
-  long i = start + tid;
-  for (; i + (ILP - 1) * (long)blockDim.x < end; i += ILP * blockDim.x) {
-    int r[ILP];
-    long long gq[ILP];
-    unsigned long long hq[ILP];
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) r[u] = rows[i + u * blockDim.x];
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-      gq[u] = (long long)llrint((double)grad[r[u]] * scale_g);
-      hq[u] = CNT_ONE
-              | (unsigned long long)llrint((double)hess[r[u]] * scale_h);
-    }
-#pragma unroll
-    for (int q = 0; q < GPB; ++q) {
-      const int grp = gq0 + q;
-      if (grp >= ngroups) break;
-      uchar4 b4[ILP];
-#pragma unroll
-      for (int u = 0; u < ILP; ++u)
-        b4[u] = binned[(size_t)grp * n_rows + r[u]];
-#pragma unroll
-      for (int u = 0; u < ILP; ++u) {
-        const unsigned char bs[4] = {b4[u].x, b4[u].y, b4[u].z, b4[u].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          unsigned long long* cell =
-              &lds64[((q * 4 + j) * n_bins + bs[j]) * 2];
-          atomicAdd(cell + 0, (unsigned long long)gq[u]);
-          atomicAdd(cell + 1, hq[u]);
-        }
-      }
-    }
-  }
-  for (; i < end; i += blockDim.x) {  // tail
-    const int r = rows[i];
-    const long long gq = (long long)llrint((double)grad[r] * scale_g);
-    const unsigned long long hq =
-        CNT_ONE | (unsigned long long)llrint((double)hess[r] * scale_h);
-#pragma unroll
-    for (int q = 0; q < GPB; ++q) {
-      const int grp = gq0 + q;
-      if (grp >= ngroups) break;
-      const uchar4 b4 = binned[(size_t)grp * n_rows + r];
-      const unsigned char bs[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        unsigned long long* cell = &lds64[((q * 4 + j) * n_bins + bs[j]) * 2];
-        atomicAdd(cell + 0, (unsigned long long)gq);
-        atomicAdd(cell + 1, hq);
-      }
-    }
-  }
-  __syncthreads();
-
-  // flush: unpack (count | h) and add to global int64 hist (nf, n_bins, 3)
-  const int valid_f = min(nfb, (ngroups - gq0) * 4);
-  for (int i = tid; i < valid_f * n_bins; i += blockDim.x) {
-    const int f = i / n_bins;
-    const int b = i % n_bins;
-    const unsigned long long gsum = lds64[(f * n_bins + b) * 2 + 0];
-    const unsigned long long hpacked = lds64[(f * n_bins + b) * 2 + 1];
-    if (gsum == 0ull && hpacked == 0ull) continue;
-    const unsigned long long cnt = hpacked >> 44;
-    const unsigned long long hsum = hpacked & ((1ull << 44) - 1ull);
-    long long* out = hist + ((size_t)(gq0 * 4 + f) * n_bins + b) * 3;
-    atomicAdd((unsigned long long*)(out + 0), gsum);
-    atomicAdd((unsigned long long*)(out + 1), hsum);
-    atomicAdd((unsigned long long*)(out + 2), cnt);
-  }
-}
-
-// --------------------------------------------- paired-plane fixed histogram
+//
 // binned_pair: (npairs, n_rows) u64, low 4B = group 2p's uchar4, high 4B =
 // group 2p+1's.  A gathered row costs ONE cacheline per feature-chunk block
-// instead of two (the two planes of a GPB=2 block are ~40 MB apart in the
-// plane-major layout, so every sparse row paid two line fetches; measured
-// 2.3x gather penalty on mid-size leaves, tools/hist_gather_probe.py).
+// instead of two (the two planes of a two-group block are ~40 MB apart in
+// the plane-major layout, so every sparse row paid two line fetches; measured
+// 2.3x gather penalty on mid-size leaves, profiles/r01_hist_gather_probe.txt).
 // Trailing-group padding (odd ngroups) accumulates into pad features that
 // the split scan masks out via nf_real.
-// GHQ=true: grad/hess come pre-quantized as one 16B record per row
-// ((gq:i64, CNT|hq:u64) in ghq) — each pair-block then gathers 2 cachelines
-// per sparse row (binned + ghq) instead of 3 (binned + grad + hess), and
-// the double->fixed conversion runs once per row instead of once per
-// (row, pair-block).
-template <bool GHQ>
 __global__ void hist_build_fixed_pair_k(
     const unsigned long long* __restrict__ binned_pair, long n_rows,
     const int* __restrict__ rows, long m, const float* __restrict__ grad,
-    const float* __restrict__ hess, const longlong2* __restrict__ ghq,
-    long long* __restrict__ hist, int n_bins,
-    int npairs, int tail_bytes, long chunk, double scale_g, double scale_h,
-    const int* __restrict__ nl_dev, int side) {
-  long base = 0, m_eff = m;
-  if (side >= 0) {
-    const long nl = nl_dev[0];
-    m_eff = (side == 0) ? nl : m - nl;
-    base = (side == 0) ? 0 : nl;
-  }
-  if ((long)blockIdx.x * chunk >= m_eff) return;
-  rows += base;
+    const float* __restrict__ hess, long long* __restrict__ hist, int n_bins,
+    int npairs, int tail_bytes, long chunk, double scale_g, double scale_h) {
   extern __shared__ unsigned long long lds64[];  // [8][n_bins][2]
   const int tid = threadIdx.x;
   const int lds_elems = 8 * n_bins * 2;
@@ -230,7 +106,7 @@ __global__ void hist_build_fixed_pair_k(
   const int jmax = (pair == npairs - 1) ? tail_bytes : 8;
   const unsigned long long* plane = binned_pair + (size_t)pair * n_rows;
   const long start = (long)blockIdx.x * chunk;
-  const long end = min(start + chunk, m_eff);
+  const long end = min(start + chunk, m);
   constexpr unsigned long long CNT_ONE = 1ull << 44;
 
   constexpr int ILP = 4;
@@ -245,15 +121,9 @@ __global__ void hist_build_fixed_pair_k(
     for (int u = 0; u < ILP; ++u) v[u] = plane[r[u]];
 #pragma unroll
     for (int u = 0; u < ILP; ++u) {
-      if (GHQ) {
-        const longlong2 q = ghq[r[u]];
-        gq[u] = q.x;
-        hq[u] = (unsigned long long)q.y;
-      } else {
-        gq[u] = (long long)llrint((double)grad[r[u]] * scale_g);
-        hq[u] = CNT_ONE
-                | (unsigned long long)llrint((double)hess[r[u]] * scale_h);
-      }
+      gq[u] = (long long)llrint((double)grad[r[u]] * scale_g);
+      hq[u] = CNT_ONE
+              | (unsigned long long)llrint((double)hess[r[u]] * scale_h);
     }
 #pragma unroll
     for (int u = 0; u < ILP; ++u) {
@@ -270,16 +140,9 @@ __global__ void hist_build_fixed_pair_k(
   for (; i < end; i += blockDim.x) {  // tail
     const int r = rows[i];
     const unsigned long long v = plane[r];
-    long long gq;
-    unsigned long long hq;
-    if (GHQ) {
-      const longlong2 q = ghq[r];
-      gq = q.x;
-      hq = (unsigned long long)q.y;
-    } else {
-      gq = (long long)llrint((double)grad[r] * scale_g);
-      hq = CNT_ONE | (unsigned long long)llrint((double)hess[r] * scale_h);
-    }
+    const long long gq = (long long)llrint((double)grad[r] * scale_g);
+    const unsigned long long hq =
+        CNT_ONE | (unsigned long long)llrint((double)hess[r] * scale_h);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (j >= jmax) break;
@@ -307,103 +170,18 @@ __global__ void hist_build_fixed_pair_k(
   }
 }
 
-// one-shot per tree: quantize grad/hess to (gq, CNT|hq) 16B records
-__global__ void quantize_gh_k(const float* __restrict__ grad,
-                              const float* __restrict__ hess, long n,
-                              double scale_g, double scale_h,
-                              longlong2* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  longlong2 q;
-  q.x = (long long)llrint((double)grad[i] * scale_g);
-  q.y = (long long)((1ull << 44)
-                    | (unsigned long long)llrint((double)hess[i] * scale_h));
-  out[i] = q;
-}
-
-extern "C" void launch_quantize_gh(const float* grad, const float* hess,
-                                   long n, double scale_g, double scale_h,
-                                   void* out, hipStream_t stream) {
-  if (n == 0) return;
-  const long blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(quantize_gh_k, dim3((unsigned)blocks), dim3(256), 0,
-                     stream, grad, hess, n, scale_g, scale_h,
-                     (longlong2*)out);
-}
-
 extern "C" void launch_hist_build_fixed_pair(
     const void* binned_pair, long n_rows, const int* rows, long m,
-    const float* grad, const float* hess, const void* ghq, long long* hist,
-    int n_bins, int npairs, int tail_bytes, double scale_g, double scale_h,
-    const int* nl_dev, int side, hipStream_t stream) {
-  if (m == 0) return;
-  long chunks = (2048 + npairs - 1) / npairs;
-  long chunk = (m + chunks - 1) / chunks;
-  if (chunk < 16384) {
-    chunk = (m + 7) / 8;
-    if (chunk < 2048) chunk = 2048;
-    if (chunk > 16384) chunk = 16384;
-  }
-  if (chunk > (1l << 19)) chunk = 1l << 19;
-  chunks = (m + chunk - 1) / chunk;
-  dim3 grid((unsigned)chunks, (unsigned)npairs);
-  const size_t lds_bytes = (size_t)8 * n_bins * 2 * sizeof(long long);
-  if (ghq) {
-    hipLaunchKernelGGL(hist_build_fixed_pair_k<true>, grid, dim3(256),
-                       lds_bytes, stream,
-                       (const unsigned long long*)binned_pair, n_rows, rows,
-                       m, grad, hess, (const longlong2*)ghq, hist, n_bins,
-                       npairs, tail_bytes, chunk, scale_g, scale_h, nl_dev,
-                       side);
-  } else {
-    hipLaunchKernelGGL(hist_build_fixed_pair_k<false>, grid, dim3(256),
-                       lds_bytes, stream,
-                       (const unsigned long long*)binned_pair, n_rows, rows,
-                       m, grad, hess, nullptr, hist, n_bins, npairs,
-                       tail_bytes, chunk, scale_g, scale_h, nl_dev, side);
-  }
-}
-
-extern "C" void launch_hist_build_fixed_child(
-    const void* binned, long n_rows, const int* rows, long m,
     const float* grad, const float* hess, long long* hist, int n_bins,
-    int ngroups, double scale_g, double scale_h, const int* nl_dev, int side,
+    int npairs, int tail_bytes, double scale_g, double scale_h,
     hipStream_t stream) {
   if (m == 0) return;
-  constexpr int GPB = 2;
-  const int n_fblocks = (ngroups + GPB - 1) / GPB;
-  long chunks = (2048 + n_fblocks - 1) / n_fblocks;
-  long chunk = (m + chunks - 1) / chunks;
-  if (chunk < 16384) {
-    chunk = (m + 7) / 8;
-    if (chunk < 2048) chunk = 2048;
-    if (chunk > 16384) chunk = 16384;
-  }
-  if (chunk > (1l << 19)) chunk = 1l << 19;
-  chunks = (m + chunk - 1) / chunk;  // m = parent size: grid upper bound
-  dim3 grid((unsigned)chunks, (unsigned)n_fblocks);
-  const size_t lds_bytes = (size_t)GPB * 4 * n_bins * 2 * sizeof(long long);
-  hipLaunchKernelGGL((hist_build_fixed_k<GPB>), grid, dim3(256), lds_bytes,
-                     stream, (const uchar4*)binned, n_rows, rows, m, grad,
-                     hess, hist, n_bins, ngroups, chunk, scale_g, scale_h,
-                     nl_dev, side);
-}
-
-extern "C" void launch_hist_build_fixed(const void* binned, long n_rows,
-                                        const int* rows, long m,
-                                        const float* grad, const float* hess,
-                                        long long* hist, int n_bins,
-                                        int ngroups, double scale_g,
-                                        double scale_h, hipStream_t stream) {
-  if (m == 0) return;
-  constexpr int GPB = 2;
-  const int n_fblocks = (ngroups + GPB - 1) / GPB;
-  long chunks = (2048 + n_fblocks - 1) / n_fblocks;
+  long chunks = (2048 + npairs - 1) / npairs;
   long chunk = (m + chunks - 1) / chunks;
   // every block flushes its whole LDS histogram with GLOBAL atomics, so
   // large leaves must not shatter into hundreds of row-chunks (profiled:
   // flush contention made calls ~0.3 ms at ~157 chunks) — but a SMALL leaf
-  // at one coarse chunk uses only n_fblocks workgroups of a 256-CU chip, so
+  // at one coarse chunk uses only npairs workgroups of a 256-CU chip, so
   // give small leaves at least 8 row-chunks (8-way flush contention is
   // negligible; measured floor drops ~3x)
   if (chunk < 16384) {
@@ -413,21 +191,12 @@ extern "C" void launch_hist_build_fixed(const void* binned, long n_rows,
   }
   if (chunk > (1l << 19)) chunk = 1l << 19;  // count-field bound (< 2^20)
   chunks = (m + chunk - 1) / chunk;
-  dim3 grid((unsigned)chunks, (unsigned)n_fblocks);
-  const size_t lds_bytes = (size_t)GPB * 4 * n_bins * 2 * sizeof(long long);
-  hipLaunchKernelGGL((hist_build_fixed_k<GPB>), grid, dim3(256), lds_bytes,
-                     stream, (const uchar4*)binned, n_rows, rows, m, grad,
-                     hess, hist, n_bins, ngroups, chunk, scale_g, scale_h,
-                     nullptr, -1);
-}
-
-static int hist_gpb_env() {
-  const char* e = getenv("MMLSPARK_HIST_GPB");
-  if (e) {
-    int v = atoi(e);
-    if (v == 1 || v == 2 || v == 4 || v == 8) return v;
-  }
-  return 4;
+  dim3 grid((unsigned)chunks, (unsigned)npairs);
+  const size_t lds_bytes = (size_t)8 * n_bins * 2 * sizeof(long long);
+  hipLaunchKernelGGL(hist_build_fixed_pair_k, grid, dim3(256), lds_bytes,
+                     stream, (const unsigned long long*)binned_pair, n_rows,
+                     rows, m, grad, hess, hist, n_bins, npairs, tail_bytes,
+                     chunk, scale_g, scale_h);
 }
 
 extern "C" void launch_hist_build(const void* binned, long n_rows,
@@ -435,7 +204,7 @@ extern "C" void launch_hist_build(const void* binned, long n_rows,
                                   const float* hess, float* hist, int n_bins,
                                   int ngroups, hipStream_t stream) {
   if (m == 0) return;
-  const int GPB = hist_gpb_env();
+  constexpr int GPB = 4;
   const int n_fblocks = (ngroups + GPB - 1) / GPB;
   // target ≥ 2048 workgroups total to fill 256 CUs × 8 XCDs
   long chunks = (2048 + n_fblocks - 1) / n_fblocks;
@@ -445,17 +214,9 @@ extern "C" void launch_hist_build(const void* binned, long n_rows,
   chunks = (m + chunk - 1) / chunk;
   dim3 grid((unsigned)chunks, (unsigned)n_fblocks);
   const size_t lds_bytes = (size_t)GPB * 4 * n_bins * 3 * sizeof(float);
-#define LAUNCH_HB(G) \
-    hipLaunchKernelGGL((hist_build_k<G>), grid, dim3(256), lds_bytes, stream, \
-                       (const uchar4*)binned, n_rows, rows, m, grad, hess,    \
-                       hist, n_bins, ngroups, chunk)
-  switch (GPB) {
-    case 1: LAUNCH_HB(1); break;
-    case 2: LAUNCH_HB(2); break;
-    case 8: LAUNCH_HB(8); break;
-    default: LAUNCH_HB(4); break;
-  }
-#undef LAUNCH_HB
+  hipLaunchKernelGGL((hist_build_k<GPB>), grid, dim3(256), lds_bytes, stream,
+                     (const uchar4*)binned, n_rows, rows, m, grad, hess,
+                     hist, n_bins, ngroups, chunk);
 }
 
 // -------------------------------------------------------- ordered partition
@@ -572,8 +333,8 @@ __global__ void part_scatter_k(const uchar4* __restrict__ binned, long n_rows,
 // records + original row ids.  Every split SCATTERS the parent's segment
 // into the other buffer (left|right, stable), so child histograms read
 // CONTIGUOUS rows — the sparse row gather that bounded child hist builds
-// (tools/hist_gather_probe.py: 2.3x) disappears entirely, at the cost of
-// moving ~124 B/row/split of arena payload (HBM streaming, ~8 TB/s).
+// (profiles/r01_hist_gather_probe.txt: 2.3x) disappears entirely, at the
+// cost of moving ~124 B/row/split of arena payload (HBM streaming, ~8 TB/s).
 
 __global__ void arena_gather_k(const unsigned long long* __restrict__ pair_src,
                                long n_src, const float* __restrict__ grad,
@@ -2076,80 +1837,65 @@ extern "C" void launch_tree_shap_csr(
 // DatasetAggregator.scala:442); implicit zeros are corrected host-side by
 // subtraction from exact integer leaf totals (LightGBM zero-bin trick).
 // Fixed-point int64 global atomics keep the multi-rank all_reduce bit-exact.
-// Thread-per-row grid-stride; rows are sorted so indptr/grad reads coalesce.
-__global__ void csr_hist_fixed_k(const long* __restrict__ indptr,
-                                 const int* __restrict__ col,
-                                 const unsigned char* __restrict__ binv,
-                                 const long long* __restrict__ gq,
-                                 const long long* __restrict__ hq,
-                                 const int* __restrict__ rows, long m,
-                                 long long* __restrict__ hist, int n_bins) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
-       i += (long)gridDim.x * blockDim.x) {
-    const int r = rows[i];
-    const unsigned long long g = (unsigned long long)gq[r];
-    const unsigned long long h = (unsigned long long)hq[r];
-    const long s = indptr[r], e = indptr[r + 1];
-    for (long j = s; j < e; ++j) {
-      unsigned long long* cell = (unsigned long long*)hist
-          + ((size_t)col[j] * n_bins + binv[j]) * 3;
-      atomicAdd(cell + 0, g);
-      atomicAdd(cell + 1, h);
-      atomicAdd(cell + 2, 1ull);
+
+// Row staging shared by both sparse histogram kernels: the wave's (up to)
+// 64 rows rows[base, base + nrows) put their entry start, quantized (g,h)
+// and the inclusive prefix of their lengths (at +1; s_len has 65 slots)
+// into the wave's LDS slices; with count_tot the lane's leaf totals grow by
+// its row.  Returns nrows; the caller's barrier publishes the slices.
+DEV_INLINE int csr_stage_wave_rows(const long* __restrict__ indptr,
+                                   const long long* __restrict__ gq,
+                                   const long long* __restrict__ hq,
+                                   const int* __restrict__ rows, long m,
+                                   long base, int lane, bool count_tot,
+                                   long* s_start, int* s_len, long long* s_g,
+                                   long long* s_h, unsigned long long& tg,
+                                   unsigned long long& th,
+                                   unsigned long long& tc) {
+  const int nrows = (int)max(0l, min((long)64, m - base));
+  long my_len = 0;
+  if (lane < nrows) {
+    const int r = rows[base + lane];
+    const long s = indptr[r];
+    s_start[lane] = s;
+    my_len = indptr[r + 1] - s;
+    const long long g = gq[r];
+    const long long h = hq[r];
+    s_g[lane] = g;
+    s_h[lane] = h;
+    if (count_tot) {
+      tg += (unsigned long long)g;
+      th += (unsigned long long)h;
+      tc += 1;
     }
   }
-}
-
-extern "C" void launch_csr_hist_fixed(const long* indptr, const int* col,
-                                      const unsigned char* binv,
-                                      const long long* gq,
-                                      const long long* hq, const int* rows,
-                                      long m, long long* hist, int n_bins,
-                                      hipStream_t stream) {
-  if (m == 0) return;
-  const int threads = 256;
-  const long want = (m + threads - 1) / threads;
-  const int blocks = (int)(want < 8192 ? want : 8192);  // ≫256 WGs, 8 XCDs
-  hipLaunchKernelGGL(csr_hist_fixed_k, dim3(blocks), dim3(threads), 0,
-                     stream, indptr, col, binv, gq, hq, rows, m, hist,
-                     n_bins);
-}
-
-// Bin of one feature per row: binary search the row's sorted column
-// segment; missing -> the feature's zero bin. Used for leaf partition.
-__global__ void csr_gather_bin_k(const long* __restrict__ indptr,
-                                 const int* __restrict__ col,
-                                 const unsigned char* __restrict__ binv,
-                                 const int* __restrict__ rows, long m,
-                                 int feature, int zero_bin,
-                                 int* __restrict__ out) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
-       i += (long)gridDim.x * blockDim.x) {
-    const int r = rows[i];
-    long lo = indptr[r], hi = indptr[r + 1];
-    int b = zero_bin;
-    while (lo < hi) {
-      const long mid = (lo + hi) >> 1;
-      const int c = col[mid];
-      if (c == feature) { b = binv[mid]; break; }
-      if (c < feature) lo = mid + 1; else hi = mid;
-    }
-    out[i] = b;
+  s_len[0] = 0;
+  int v = (int)my_len;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up((int)v, d);
+    if (lane >= d) v += up;
   }
+  s_len[lane + 1] = v;
+  return nrows;
 }
 
-extern "C" void launch_csr_gather_bin(const long* indptr, const int* col,
-                                      const unsigned char* binv,
-                                      const int* rows, long m, int feature,
-                                      int zero_bin, int* out,
-                                      hipStream_t stream) {
-  if (m == 0) return;
-  const int threads = 256;
-  const long want = (m + threads - 1) / threads;
-  const int blocks = (int)(want < 8192 ? want : 8192);
-  hipLaunchKernelGGL(csr_gather_bin_k, dim3(blocks), dim3(threads), 0,
-                     stream, indptr, col, binv, rows, m, feature, zero_bin,
-                     out);
+// wave-reduce the lanes' leaf totals, one atomic triple per wave
+DEV_INLINE void csr_add_wave_totals(unsigned long long tg,
+                                    unsigned long long th,
+                                    unsigned long long tc, int lane,
+                                    long long* __restrict__ tot) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    tg += (unsigned long long)__shfl_down((long long)tg, d);
+    th += (unsigned long long)__shfl_down((long long)th, d);
+    tc += (unsigned long long)__shfl_down((long long)tc, d);
+  }
+  if (lane == 0 && tot) {
+    atomicAdd((unsigned long long*)tot + 0, tg);
+    atomicAdd((unsigned long long*)tot + 1, th);
+    atomicAdd((unsigned long long*)tot + 2, tc);
+  }
 }
 
 // v2 sparse histogram: one WAVE cooperates on 64 consecutive rows of the
@@ -2178,31 +1924,9 @@ __global__ void csr_hist_fixed_v2_k(const long* __restrict__ indptr,
   // barriers below must not diverge); each wave owns a 64-row sub-chunk
   for (long bbase = (long)blockIdx.x * 256; bbase < m;
        bbase += (long)gridDim.x * 256) {
-    const long base = bbase + (long)wid * 64;
-    const int nrows = (int)max(0l, min((long)64, m - base));
-    long my_len = 0;
-    if (lane < nrows) {
-      const int r = rows[base + lane];
-      const long s = indptr[r];
-      s_start[wid][lane] = s;
-      my_len = indptr[r + 1] - s;
-      const long long g = gq[r];
-      const long long h = hq[r];
-      s_g[wid][lane] = g;
-      s_h[wid][lane] = h;
-      tg += (unsigned long long)g;
-      th += (unsigned long long)h;
-      tc += 1;
-    }
-    // inclusive prefix of row lengths across the wave (LDS scan)
-    s_len[wid][0] = 0;
-    int v = (int)my_len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up((int)v, d);
-      if (lane >= d) v += up;
-    }
-    s_len[wid][lane + 1] = v;
+    const int nrows = csr_stage_wave_rows(
+        indptr, gq, hq, rows, m, bbase + (long)wid * 64, lane, true,
+        s_start[wid], s_len[wid], s_g[wid], s_h[wid], tg, th, tc);
     __syncthreads();
     const int total = s_len[wid][nrows];
     const int* cum = s_len[wid];
@@ -2222,18 +1946,7 @@ __global__ void csr_hist_fixed_v2_k(const long* __restrict__ indptr,
     }
     __syncthreads();
   }
-  // wave-reduce totals, one atomic triple per wave
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    tg += (unsigned long long)__shfl_down((long long)tg, d);
-    th += (unsigned long long)__shfl_down((long long)th, d);
-    tc += (unsigned long long)__shfl_down((long long)tc, d);
-  }
-  if (lane == 0 && tot) {
-    atomicAdd((unsigned long long*)tot + 0, tg);
-    atomicAdd((unsigned long long*)tot + 1, th);
-    atomicAdd((unsigned long long*)tot + 2, tc);
-  }
+  csr_add_wave_totals(tg, th, tc, lane, tot);
 }
 
 extern "C" void launch_csr_hist_fixed_v2(const long* indptr, const int* col,
@@ -2261,7 +1974,7 @@ extern "C" void launch_csr_hist_fixed_v2(const long* indptr, const int* col,
 // LDS cell.  Row staging + entry→row mapping as in v2.  Row count per
 // block must stay ≤ 2^19 so the 44-bit packed h-sum cannot overflow
 // (launcher enforces via grid sizing).
-template <int FW, bool ILP = false>  // FW: feature-chunk width; ILP: 4-entry load batching
+template <int FW>  // FW: feature-chunk width
 __global__ void csr_hist_fixed_lds_k(const long* __restrict__ indptr,
                                      const int* __restrict__ col,
                                      const unsigned char* __restrict__ binv,
@@ -2288,32 +2001,11 @@ __global__ void csr_hist_fixed_lds_k(const long* __restrict__ indptr,
 
   for (long bbase = (long)blockIdx.x * 256; bbase < m;
        bbase += (long)gridDim.x * 256) {
-    const long base = bbase + (long)wid * 64;
-    const int nrows = (int)max(0l, min((long)64, m - base));
-    long my_len = 0;
-    if (lane < nrows) {
-      const int r = rows[base + lane];
-      const long s = indptr[r];
-      s_start[wid][lane] = s;
-      my_len = indptr[r + 1] - s;
-      const long long g = gq[r];
-      const long long h = hq[r];
-      s_g[wid][lane] = g;
-      s_h[wid][lane] = h;
-      if (blockIdx.y == 0) {  // totals once, not per feature chunk
-        tg += (unsigned long long)g;
-        th += (unsigned long long)h;
-        tc += 1;
-      }
-    }
-    s_len[wid][0] = 0;
-    int v = (int)my_len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up((int)v, d);
-      if (lane >= d) v += up;
-    }
-    s_len[wid][lane + 1] = v;
+    // totals once (blockIdx.y == 0), not per feature chunk
+    const int nrows = csr_stage_wave_rows(
+        indptr, gq, hq, rows, m, bbase + (long)wid * 64, lane,
+        blockIdx.y == 0, s_start[wid], s_len[wid], s_g[wid], s_h[wid], tg,
+        th, tc);
     __syncthreads();
     // contiguous per-lane entry ranges: ONE binary search per lane, then
     // an amortized forward row walk — the strided variant's per-entry
@@ -2329,46 +2021,15 @@ __global__ void csr_hist_fixed_lds_k(const long* __restrict__ indptr,
         const int mid = (k + hi2) >> 1;
         if (cum[mid] <= e0) k = mid; else hi2 = mid;
       }
-      if (ILP) {
-        // batch 4 entries: resolve rows + issue all col/bin loads before
-        // any LDS atomic.  A/B-measured on MI355X @10M×100 nnz=20: 131M vs
-        // 211M rows/s — 1.6× SLOWER (the ks/js/cs/bs staging spills and the
-        // LDS-atomic chain, not load latency, is the bound).  Kept gated
-        // OFF behind MMLSPARK_AMD_SPARSE_ILP as the recorded negative result
-        for (int e = e0; e < e1;) {
-          int ks[4]; long js[4]; int cnt = 0;
-          for (; cnt < 4 && e + cnt < e1; ++cnt) {
-            while (cum[k + 1] <= e + cnt) ++k;
-            ks[cnt] = k;
-            js[cnt] = s_start[wid][k] + (e + cnt - cum[k]);
-          }
-          int cs[4]; unsigned char bs[4];
-          for (int t = 0; t < cnt; ++t) {
-            cs[t] = col[js[t]];
-            bs[t] = binv[js[t]];
-          }
-          for (int t = 0; t < cnt; ++t) {
-            if (cs[t] >= f0 && cs[t] < f0 + FW) {
-              unsigned long long* cell =
-                  &lds64[(((cs[t] - f0) * n_bins) + bs[t]) * 2];
-              atomicAdd(cell + 0, (unsigned long long)s_g[wid][ks[t]]);
-              atomicAdd(cell + 1,
-                        CNT_ONE + (unsigned long long)s_h[wid][ks[t]]);
-            }
-          }
-          e += cnt;
-        }
-      } else {
-        for (int e = e0; e < e1; ++e) {
-          while (cum[k + 1] <= e) ++k;
-          const long j = s_start[wid][k] + (e - cum[k]);
-          const int c = col[j];
-          if (c >= f0 && c < f0 + FW) {
+      for (int e = e0; e < e1; ++e) {
+        while (cum[k + 1] <= e) ++k;
+        const long j = s_start[wid][k] + (e - cum[k]);
+        const int c = col[j];
+        if (c >= f0 && c < f0 + FW) {
           unsigned long long* cell =
               &lds64[(((c - f0) * n_bins) + binv[j]) * 2];
           atomicAdd(cell + 0, (unsigned long long)s_g[wid][k]);
           atomicAdd(cell + 1, CNT_ONE + (unsigned long long)s_h[wid][k]);
-          }
         }
       }
     }
@@ -2388,19 +2049,7 @@ __global__ void csr_hist_fixed_lds_k(const long* __restrict__ indptr,
               hpacked & ((1ull << 44) - 1ull));
     atomicAdd((unsigned long long*)(out + 2), hpacked >> 44);
   }
-  if (blockIdx.y == 0) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      tg += (unsigned long long)__shfl_down((long long)tg, d);
-      th += (unsigned long long)__shfl_down((long long)th, d);
-      tc += (unsigned long long)__shfl_down((long long)tc, d);
-    }
-    if (lane == 0 && tot) {
-      atomicAdd((unsigned long long*)tot + 0, tg);
-      atomicAdd((unsigned long long*)tot + 1, th);
-      atomicAdd((unsigned long long*)tot + 2, tc);
-    }
-  }
+  if (blockIdx.y == 0) csr_add_wave_totals(tg, th, tc, lane, tot);
 }
 
 extern "C" void launch_csr_hist_fixed_lds(const long* indptr, const int* col,
@@ -2420,40 +2069,17 @@ extern "C" void launch_csr_hist_fixed_lds(const long* indptr, const int* col,
   // A/B-measured on MI355X at 10M×100 nnz=20: FW=16 (half the passes,
   // half the occupancy) ties FW=8; FW=4 (more occupancy, double passes)
   // is ~1.7× SLOWER — reads win over latency hiding below FW=8, atomics
-  // cap above it.  FW=8 is the sweet spot and the default
-  static const int fw_env = [] {
-    const char* e = getenv("MMLSPARK_AMD_SPARSE_FW");
-    return e ? atoi(e) : 8;
-  }();
-  static const bool ilp_env = [] {
-    const char* e = getenv("MMLSPARK_AMD_SPARSE_ILP");
-    return e && atoi(e) != 0;
-  }();
-  const int FW = (fw_env == 16) ? 16 : (fw_env == 4 ? 4 : 8);
+  // cap above it, so FW is fixed at 8.  Batching 4 entries' col/bin loads
+  // ahead of the LDS atomics in the entry walk measured 131M vs 211M rows/s
+  // on the same workload, 1.6× SLOWER (the staging spills, and the
+  // LDS-atomic chain, not load latency, is the bound)
+  constexpr int FW = 8;
   const int by = (nf + FW - 1) / FW;
   const size_t lds_bytes = (size_t)FW * n_bins * 2 * sizeof(long long);
-  if (FW == 8 && ilp_env) {
-    hipLaunchKernelGGL((csr_hist_fixed_lds_k<8, true>),
-                       dim3((unsigned)bx, (unsigned)by), dim3(256),
-                       lds_bytes, stream, indptr, col, binv, gq, hq, rows,
-                       m, hist, n_bins, nf, tot);
-    return;
-  }
-  if (FW == 4)
-    hipLaunchKernelGGL(csr_hist_fixed_lds_k<4>,
-                       dim3((unsigned)bx, (unsigned)by), dim3(256),
-                       lds_bytes, stream, indptr, col, binv, gq, hq, rows,
-                       m, hist, n_bins, nf, tot);
-  else if (FW == 8)
-    hipLaunchKernelGGL(csr_hist_fixed_lds_k<8>,
-                       dim3((unsigned)bx, (unsigned)by), dim3(256),
-                       lds_bytes, stream, indptr, col, binv, gq, hq, rows,
-                       m, hist, n_bins, nf, tot);
-  else
-    hipLaunchKernelGGL(csr_hist_fixed_lds_k<16>,
-                       dim3((unsigned)bx, (unsigned)by), dim3(256),
-                       lds_bytes, stream, indptr, col, binv, gq, hq, rows,
-                       m, hist, n_bins, nf, tot);
+  hipLaunchKernelGGL(csr_hist_fixed_lds_k<FW>,
+                     dim3((unsigned)bx, (unsigned)by), dim3(256), lds_bytes,
+                     stream, indptr, col, binv, gq, hq, rows, m, hist, n_bins,
+                     nf, tot);
 }
 
 // Fused CSR leaf partition: predicate = binary-searched bin of the split

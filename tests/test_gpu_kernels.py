@@ -171,6 +171,19 @@ def test_split_scan_matches_cpu():
         assert torch.allclose(ref[:, 3:], out[:, 3:], rtol=1e-3, atol=1e-2)
 
 
+def _pair_planes(binned):
+    """(ngroups, n, 4) uint8 device planes -> ((npairs, n) int64 paired
+    planes, tail_bytes), paired exactly as TreeGrower.__init__ pairs them."""
+    g32 = binned.view(torch.int32).reshape(binned.shape[0], -1)
+    ngroups = g32.shape[0]
+    if ngroups % 2:
+        g32 = torch.cat([g32, torch.zeros_like(g32[:1])])
+    lo = g32[0::2].to(torch.int64) & 0xFFFFFFFF
+    hi = g32[1::2].to(torch.int64) & 0xFFFFFFFF
+    pair = (lo | (hi << 32)).contiguous()
+    return pair, ngroups * 4 - (pair.shape[0] - 1) * 8
+
+
 @requires_gpu
 def test_hist_build_fixed_matches_cpu():
     from mmlspark_amd.ops import backend, cpu_ref
@@ -187,8 +200,10 @@ def test_hist_build_fixed_matches_cpu():
     hmax = float(hess.max())
     sg = (2.0 ** 61) / (n * gmax)
     sh = (2.0 ** 24) / hmax
-    out = backend.hist_build_fixed(binned.cuda(), rows.cuda(), grad.cuda(),
-                                   hess.cuda(), nb, sg, sh).cpu()
+    pair, tail = _pair_planes(binned.cuda())
+    out = backend.hist_build_fixed_pair(pair, rows.cuda(), grad.cuda(),
+                                        hess.cuda(), nb, tail, sg,
+                                        sh)[:ngroups * 4].cpu()
     outf = out.double() * torch.tensor([1.0 / sg, 1.0 / sh, 1.0]).double()
     assert torch.equal(outf[:, :, 2].float(), ref[:, :, 2])  # counts exact
     assert torch.allclose(outf[:, :, 0].float(), ref[:, :, 0], atol=2e-3,
@@ -396,32 +411,27 @@ def test_native_grower_device_count_path(binary_df):
 
 
 @requires_gpu
-def test_hist_build_fixed_pair_matches_unpaired():
-    """Paired-plane histogram == unpaired fixed-point histogram exactly
-    (same fixed-point integers, one 8B load per row per block)."""
-    from mmlspark_amd.ops import backend
+def test_hist_build_fixed_pair_matches_cpu_integers():
+    """Paired-plane histogram == the CPU's exact fixed-point integer
+    histogram (same rounding per row, order-free int64 sums)."""
+    from mmlspark_amd.ops import backend, cpu_ref
     g = torch.Generator().manual_seed(13)
     n, nf, nb = 300_000, 26, 255  # odd group count → zero-padded high plane
     ngroups = (nf + 3) // 4
     binned = torch.randint(0, nb, (ngroups, n, 4), generator=g,
-                           dtype=torch.uint8).cuda()
-    g32 = binned.view(torch.int32).reshape(ngroups, -1)
-    if ngroups % 2:
-        g32 = torch.cat([g32, torch.zeros_like(g32[:1])])
-    lo = g32[0::2].to(torch.int64) & 0xFFFFFFFF
-    hi = g32[1::2].to(torch.int64) & 0xFFFFFFFF
-    pair = (lo | (hi << 32)).contiguous()
+                           dtype=torch.uint8)
+    pair, tail = _pair_planes(binned.cuda())
     rows = torch.randperm(n, generator=g)[: n // 4].to(
-        torch.int32).sort().values.cuda()
-    grad = torch.randn(n, generator=g).cuda()
-    hess = (torch.rand(n, generator=g) + 0.1).cuda()
+        torch.int32).sort().values
+    grad = torch.randn(n, generator=g)
+    hess = torch.rand(n, generator=g) + 0.1
     sg, sh = 2.0 ** 40 / n, 2.0 ** 24
     nf_pad = ngroups * 4
-    tail = nf_pad - (pair.shape[0] - 1) * 8
-    ref = backend.hist_build_fixed(binned, rows, grad, hess, nb, sg, sh)
-    out = backend.hist_build_fixed_pair(pair, rows, grad, hess, nb, tail,
-                                        sg, sh)
-    assert torch.equal(out[:nf_pad].cpu(), ref.cpu())
+    assert tail == 4
+    ref = cpu_ref.hist_build_fixed(binned, rows, grad, hess, nb, sg, sh)
+    out = backend.hist_build_fixed_pair(pair, rows.cuda(), grad.cuda(),
+                                        hess.cuda(), nb, tail, sg, sh)
+    assert torch.equal(out[:nf_pad].cpu(), ref)
     # zero-pad features are skipped entirely (no bin-0 atomic hotspot)
     if out.shape[0] > nf_pad:
         assert int(out[nf_pad:].abs().sum()) == 0

@@ -44,24 +44,10 @@ def test_csr_hist_kernel_matches_cpu():
     rows = torch.randperm(n, generator=gen)[: n // 3].to(
         torch.int32).sort().values
     ref = cpu_ref.csr_hist_fixed(indptr, col, binv, gq, hq, rows, nf, nb)
-    out = backend.csr_hist_fixed(indptr.cuda(), col.cuda(), binv.cuda(),
-                                 gq.cuda(), hq.cuda(), rows.cuda(), nf, nb)
+    out, _ = backend.csr_hist_fixed_tot(indptr.cuda(), col.cuda(),
+                                        binv.cuda(), gq.cuda(), hq.cuda(),
+                                        rows.cuda(), nf, nb)
     assert torch.equal(out.cpu(), ref)  # integer atomics: exact
-
-
-@requires_gpu
-def test_csr_gather_bins_kernel_matches_cpu():
-    from mmlspark_amd.ops import backend, cpu_ref
-    gen = torch.Generator().manual_seed(1)
-    n, nf = 80_000, 200
-    indptr, col, binv = _rand_csr(gen, n, nf, 6)
-    rows = torch.randperm(n, generator=gen)[: n // 2].to(
-        torch.int32).sort().values
-    for f, zb in ((0, 3), (57, 0), (199, 12)):
-        ref = cpu_ref.csr_gather_bins(indptr, col, binv, rows, f, zb)
-        out = backend.csr_gather_bins(indptr.cuda(), col.cuda(), binv.cuda(),
-                                      rows.cuda(), f, zb)
-        assert torch.equal(out.cpu(), ref)
 
 
 @requires_gpu
@@ -136,12 +122,17 @@ def test_sparse_high_dim_1m_x_100k():
 
 @requires_gpu
 def test_csr_hist_v2_fused_totals_matches_cpu():
-    """Wave-cooperative v2 kernel (LDS row staging + in-kernel totals)
-    must be integer-exact vs the reference, including ragged tails."""
+    """Wave-cooperative kernels (LDS row staging + in-kernel totals) must
+    be integer-exact vs the reference, including ragged tails.  nf <= 2048
+    runs csr_hist_fixed_lds_k, wider nf runs csr_hist_fixed_v2_k; a third of
+    the n rows are selected, so n = 900 gives 300: one full 256-row block
+    and a second whose waves hold 44, 0, 0 and 0 rows."""
     from mmlspark_amd.ops import backend, cpu_ref
     gen = torch.Generator().manual_seed(7)
     for n, nf, nb, nnz in ((50_000, 300, 31, 12), (4097, 64, 255, 3),
-                           (63, 10, 15, 5)):
+                           (63, 10, 15, 5), (300, 2048, 15, 5),
+                           (300, 2049, 15, 5), (63, 4096, 15, 5),
+                           (900, 2049, 15, 5)):
         indptr, col, binv = _rand_csr(gen, n, nf, nnz)
         binv = (binv % nb).contiguous()  # bins must lie in [0, nb)
         gq = torch.randint(-2**40, 2**40, (n,), generator=gen,
