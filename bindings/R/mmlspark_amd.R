@@ -722,7 +722,7 @@ ml_image_featurizer <- function(inputCol = NULL, outputCol = NULL, batchSize = N
   stage
 }
 
-ml_image_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, superpixelCol = NULL) {
+ml_image_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, fusedFit = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, superpixelCol = NULL) {
   stage <- mmlspark_amd$explainers$lime$ImageLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -735,6 +735,7 @@ ml_image_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, 
   if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
+  if (!is.null(fusedFit)) stage$set("fusedFit", fusedFit)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(cellSize)) stage$set("cellSize", cellSize)
   if (!is.null(modifier)) stage$set("modifier", modifier)
@@ -1601,7 +1602,7 @@ ml_summarize_data <- function(counts = NULL, basic = NULL, percentiles = NULL) {
   stage
 }
 
-ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, nIter = NULL, device = NULL) {
+ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, fusedFit = NULL, inputCol = NULL, cellSize = NULL, modifier = NULL, nIter = NULL, device = NULL) {
   stage <- mmlspark_amd$explainers$lime$SuperpixelTransformer()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1614,6 +1615,7 @@ ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClas
   if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
+  if (!is.null(fusedFit)) stage$set("fusedFit", fusedFit)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(cellSize)) stage$set("cellSize", cellSize)
   if (!is.null(modifier)) stage$set("modifier", modifier)
@@ -1622,7 +1624,7 @@ ml_superpixel_transformer <- function(model = NULL, targetCol = NULL, targetClas
   stage
 }
 
-ml_tabular_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCols = NULL, backgroundData = NULL) {
+ml_tabular_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, fusedFit = NULL, inputCols = NULL, backgroundData = NULL) {
   stage <- mmlspark_amd$explainers$lime$TabularLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1635,6 +1637,7 @@ ml_tabular_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL
   if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
+  if (!is.null(fusedFit)) stage$set("fusedFit", fusedFit)
   if (!is.null(inputCols)) stage$set("inputCols", inputCols)
   if (!is.null(backgroundData)) stage$set("backgroundData", backgroundData)
   stage
@@ -1709,7 +1712,7 @@ ml_text_featurizer_model <- function(inputCol = NULL, outputCol = NULL, useToken
   stage
 }
 
-ml_text_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, inputCol = NULL, tokensCol = NULL) {
+ml_text_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, fusedFit = NULL, inputCol = NULL, tokensCol = NULL) {
   stage <- mmlspark_amd$explainers$lime$TextLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1722,6 +1725,7 @@ ml_text_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, o
   if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
+  if (!is.null(fusedFit)) stage$set("fusedFit", fusedFit)
   if (!is.null(inputCol)) stage$set("inputCol", inputCol)
   if (!is.null(tokensCol)) stage$set("tokensCol", tokensCol)
   stage
@@ -1943,7 +1947,7 @@ ml_value_indexer_model <- function(inputCol = NULL, outputCol = NULL, levels = N
   stage
 }
 
-ml_vector_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, featuresCol = NULL, backgroundData = NULL) {
+ml_vector_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL, outputCol = NULL, numSamples = NULL, metricsCol = NULL, seed = NULL, rowBatch = NULL, fusedSampling = NULL, kernelWidth = NULL, regularization = NULL, fusedFit = NULL, featuresCol = NULL, backgroundData = NULL) {
   stage <- mmlspark_amd$explainers$lime$VectorLIME()
   if (!is.null(model)) stage$set("model", model)
   if (!is.null(targetCol)) stage$set("targetCol", targetCol)
@@ -1956,6 +1960,7 @@ ml_vector_lime <- function(model = NULL, targetCol = NULL, targetClasses = NULL,
   if (!is.null(fusedSampling)) stage$set("fusedSampling", fusedSampling)
   if (!is.null(kernelWidth)) stage$set("kernelWidth", kernelWidth)
   if (!is.null(regularization)) stage$set("regularization", regularization)
+  if (!is.null(fusedFit)) stage$set("fusedFit", fusedFit)
   if (!is.null(featuresCol)) stage$set("featuresCol", featuresCol)
   if (!is.null(backgroundData)) stage$set("backgroundData", backgroundData)
   stage

@@ -10,14 +10,19 @@ and drawn background rows to the model's score_coalitions (GBDT models: one
 fused forest kernel, no perturbed samples) and fit the lasso on its output;
 ImageLIME segments uint8 images and builds the masked model input on the GPU
 (explainers/base.py), and SuperpixelTransformer(device="cuda") segments a
-whole column in batched launches."""
+whole column in batched launches.
+With fusedFit=True the four LIME stages pack a chunk's states, send them with
+the scores to the model's device and fit every row's and class's surrogate in
+one float64 kernel launch (ops/backend.py::lime_fit) instead of one host
+lasso each; the random draws and everything before the fit are unchanged."""
 from __future__ import annotations
 
 import numpy as np
 import pandas as pd
 import torch
 
-from ..core.param import Param, toFloat, toInt, toList, toString
+from ..core.param import (Param, toBool, toFloat, toInt, toList,
+                          toString)
 from ..core.registry import register
 from ..core.schema import matrix_to_vector_column, vector_column_to_matrix
 from .base import LocalExplainer
@@ -30,6 +35,12 @@ class LIMEBase(LocalExplainer):
     kernelWidth = Param("kernelWidth", "RBF kernel width on state distance",
                         0.75, toFloat)
     regularization = Param("regularization", "lasso alpha", 0.0, toFloat)
+    fusedFit = Param("fusedFit", "fit every surrogate of a chunk (rowBatch "
+                     "rows, or one image or text) in one float64 kernel "
+                     "launch on the model's GPU instead of one host lasso "
+                     "per row and class (more than 512 features or 8 target "
+                     "classes take the host fit; without a GPU the same "
+                     "float64 fit runs on the CPU)", False, toBool)
 
     def _default_samples(self, m):
         return 1000
@@ -58,6 +69,35 @@ class LIMEBase(LocalExplainer):
         if r2_out is not None:
             r2_out.append(np.asarray(r2s))
         return np.stack(coefs)  # (n_classes, m)
+
+    def _fit_chunk(self, states_l, scores, r2_out):
+        """_fit_states of every row of a chunk: states_l holds one (n, m)
+        state matrix per row, scores their scores back to back.  With
+        fusedFit the chunk is one backend.lime_fit call on the model's
+        device."""
+        from ..ops import backend
+        from ..utils.devices import default_device
+        R = len(states_l)
+        n, m = states_l[0].shape if R else (0, 0)
+        if not (self.get("fusedFit") and n >= 1
+                and 1 <= m <= backend.LIME_FIT_MAX_FEATURES
+                and 1 <= scores.shape[1] <= backend.LIME_FIT_MAX_OUTPUTS):
+            return [self._fit_states(st, scores[i * n:(i + 1) * n],
+                                     r2_out=r2_out)
+                    for i, st in enumerate(states_l)]
+        model = self.get("model")
+        dev = default_device(model.get("device")
+                             if "device" in model.params() else "auto")
+        if dev.type == "cuda" and not torch.cuda.is_available():
+            dev = torch.device("cpu")
+        bits = torch.stack([backend.pack_states(st) for st in states_l])
+        y = torch.from_numpy(np.ascontiguousarray(
+            scores, dtype=np.float64).reshape(R, n, -1))
+        coef, _, r2, _ = backend.lime_fit(
+            bits.to(dev), m, y.to(dev), self.get("kernelWidth"),
+            self.get("regularization"))
+        r2_out.extend(r2.cpu().numpy())
+        return list(coef.cpu().numpy())
 
     def _fused_chunk_scores(self, model, bg_dev, chunk, bg, states_l, rng,
                             score_samples):
@@ -109,12 +149,7 @@ class TabularLIME(LIMEBase):
                          for x, st in zip(chunk, states_l)]
                 # one scoring fan-out for the whole chunk
                 scores = self._score_matrix(np.concatenate(perts), cols)                 if perts else np.zeros((0, 1))
-            o = 0
-            for st, p_ in zip(states_l, perts):
-                explanations.append(
-                    self._fit_states(st, scores[o:o + len(p_)],
-                                     r2_out=r2s))
-                o += len(p_)
+            explanations.extend(self._fit_chunk(states_l, scores, r2s))
         out = df.copy()
         out[self.get("outputCol")] = explanations
         if self.get("metricsCol"):
@@ -152,12 +187,7 @@ class VectorLIME(LIMEBase):
                 perts = [VectorSampler(bg, rng).apply(x, st).astype(np.float32)
                          for x, st in zip(chunk, states_l)]
                 scores = self._score_matrix(np.concatenate(perts))                 if perts else np.zeros((0, 1))
-            o = 0
-            for st, p_ in zip(states_l, perts):
-                explanations.append(
-                    self._fit_states(st, scores[o:o + len(p_)],
-                                     r2_out=r2s))
-                o += len(p_)
+            explanations.extend(self._fit_chunk(states_l, scores, r2s))
         out = df.copy()
         out[self.get("outputCol")] = explanations
         if self.get("metricsCol"):
@@ -182,8 +212,7 @@ class TextLIME(LIMEBase):
             texts = TextSampler(tokens).apply(states)
             scores = self._score_samples(
                 pd.DataFrame({self.get("inputCol"): texts}))
-            explanations.append(self._fit_states(states, scores,
-                                                 r2_out=r2s))
+            explanations.extend(self._fit_chunk([states], scores, r2s))
         out = df.copy()
         out[self.get("outputCol")] = explanations
         if self.get("metricsCol"):
@@ -222,8 +251,7 @@ class ImageLIME(LIMEBase):
                 imgs = ImageSampler(img, segments).apply(states)
                 scores = self._score_samples(
                     pd.DataFrame({self.get("inputCol"): imgs}))
-            explanations.append(self._fit_states(states, scores,
-                                                 r2_out=r2s))
+            explanations.extend(self._fit_chunk([states], scores, r2s))
         out = df.copy()
         out[self.get("outputCol")] = explanations
         if self.get("metricsCol"):

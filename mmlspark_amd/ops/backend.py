@@ -1202,6 +1202,78 @@ def masked_image_batch(image, segments, states, fill, size, lut, m=None):
                                       lut.cpu()).to(dev)
 
 
+# ---------------------------------------------------------------- LIME fit
+LIME_FIT_MAX_FEATURES = cpu_ref.LIME_FIT_MAX_FEATURES   # Gram in L2 above 128
+LIME_FIT_MAX_OUTPUTS = cpu_ref.LIME_FIT_MAX_OUTPUTS     # one wavefront each
+
+
+def check_lime_fit_inputs(states_bits, m, scores, kernel_width, alpha,
+                          max_iter, tol):
+    """Everything lime_fit indexes with, checked in O(1); raises ValueError
+    and nothing is launched."""
+    def bad(msg):
+        raise ValueError("lime_fit: " + msg)
+
+    for name, t, dtype in (("states_bits", states_bits, torch.int32),
+                           ("scores", scores, torch.float64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            bad("%s must be a %s tensor" % (name, dtype))
+        if t.dim() != 3:
+            bad(name + " must have 3 dimensions")
+        if not t.is_contiguous():
+            bad(name + " must be contiguous")
+    if scores.device != states_bits.device:
+        bad("scores must live where states_bits lives")
+    if not 1 <= int(m) <= LIME_FIT_MAX_FEATURES:
+        bad("m must be in [1, %d]" % LIME_FIT_MAX_FEATURES)
+    R, n, W = states_bits.shape
+    if W != (int(m) + 31) // 32:
+        bad("states_bits must have ceil(m / 32) words per sample")
+    if not 1 <= n < (1 << 31) or R >= (1 << 31):
+        bad("states_bits must hold 1 <= n < 2^31 samples of R < 2^31 rows")
+    if tuple(scores.shape[:2]) != (R, n):
+        bad("scores must be (R, n, C) beside states_bits (R, n, W)")
+    if not 1 <= scores.shape[2] <= LIME_FIT_MAX_OUTPUTS:
+        bad("the class count must be in [1, %d]" % LIME_FIT_MAX_OUTPUTS)
+    if not float(kernel_width) > 0 or not float(alpha) >= 0:
+        bad("kernel_width must be positive and alpha non-negative")
+    if int(max_iter) < 0 or int(max_iter) >= (1 << 31) \
+            or float(tol) != float(tol):
+        bad("max_iter must be in [0, 2^31) and tol a number")
+
+
+def lime_fit(states_bits, m, scores, kernel_width, alpha, max_iter=200,
+             tol=1e-6):
+    """Every local surrogate of a chunk of LIME rows: for row r and class c
+    the lasso of explainers/regression.py::lasso_regression on the m on/off
+    states against scores[r, :, c], weighted as LIMEBase._weights does, in
+    float64 throughout (lasso_regression rounds each coordinate update
+    through float32; this does not).  A column that is on in no sample or in
+    every sample gets coefficient exactly 0.  states_bits (R, n,
+    ceil(m / 32)) int32 from pack_states, scores (R, n, C) float64, m up to
+    LIME_FIT_MAX_FEATURES and C up to LIME_FIT_MAX_OUTPUTS.  GPU tensors go
+    to lime_fit_kernels.hip, one launch and one block per row, unless
+    MMLSPARK_AMD_LIME_FUSED=0; CPU tensors and the switch get
+    cpu_ref.lime_fit.  Returns coef (R, C, m), intercept (R, C), r2 (R, C)
+    float64 and n_sweeps (R, C) int32 on the inputs' device."""
+    import os
+    check_lime_fit_inputs(states_bits, m, scores, kernel_width, alpha,
+                          max_iter, tol)
+    args = (int(m), scores, float(kernel_width), float(alpha), int(max_iter),
+            float(tol))
+    if states_bits.is_cuda and os.environ.get(
+            "MMLSPARK_AMD_LIME_FUSED", "1") != "0":
+        ext = _require_ext()
+        if (ext.LIME_FIT_MAX_FEATURES, ext.LIME_FIT_MAX_OUTPUTS) != (
+                LIME_FIT_MAX_FEATURES, LIME_FIT_MAX_OUTPUTS):
+            raise RuntimeError("lime_fit: the built extension has other "
+                               "limits than ops/backend.py; rebuild it")
+        return tuple(ext.lime_fit(states_bits, *args))
+    dev = states_bits.device
+    out = cpu_ref.lime_fit(states_bits.cpu(), args[0], scores.cpu(), *args[2:])
+    return tuple(t.to(dev) for t in out)
+
+
 # -------------------------------------------------------- isolation forest
 IFOREST_MAX_SUB = cpu_ref.IFOREST_MAX_SUB   # one tree's subsample in one block's LDS
 

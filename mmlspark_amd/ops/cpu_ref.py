@@ -1136,6 +1136,72 @@ def masked_image_batch(image, segments, states, m, fill, size, lut):
     return batch
 
 
+# ---------------------------------------------------------------- LIME fit
+LIME_FIT_MAX_FEATURES = 512
+LIME_FIT_MAX_OUTPUTS = 8
+
+
+def lime_fit(states_bits, m, scores, kernel_width, alpha, max_iter=200,
+             tol=1e-6):
+    """The contract of ops/hip/lime_fit_kernels.hip in float64 numpy: for
+    every row r and class c the kernel-weighted lasso of
+    explainers/regression.py::lasso_regression in its residual form (same
+    cyclic order, same bnew != bj test, same max |delta| < tol stop, same
+    max_iter), with no float32 step, on the weights of LIMEBase._weights.
+    A column that is on in no sample or in every sample is constant: it is
+    left out and its coefficient is exactly 0.  states_bits (R, n,
+    ceil(m / 32)) int32 from pack_states, scores (R, n, C) float64.  Returns
+    coef (R, C, m), intercept (R, C), r2 (R, C) float64 and n_sweeps (R, C)
+    int32, the sweeps each descent ran."""
+    import numpy as np
+    bits = states_bits.numpy().view(np.uint32)
+    R, n, _ = bits.shape
+    S_all = ((bits[..., None] >> np.arange(32, dtype=np.uint32)) & 1) \
+        .reshape(R, n, -1)[:, :, :m].astype(np.float64)
+    Y_all = scores.numpy()
+    C = Y_all.shape[2]
+    coef = np.zeros((R, C, m))
+    intercept = np.zeros((R, C))
+    r2 = np.zeros((R, C))
+    sweeps = np.zeros((R, C), dtype=np.int32)
+    for r in range(R):
+        S = S_all[r]
+        d = np.sqrt((1.0 - S).sum(axis=1)) / np.sqrt(float(m))
+        w = np.sqrt(np.exp(-(d / kernel_width) ** 2))
+        w = w / w.sum()
+        on = S.sum(axis=0)
+        act = np.flatnonzero((on > 0) & (on < n))
+        xm = (S * w[:, None]).sum(0)
+        Xc = S[:, act] - xm[act]
+        xs = np.sqrt((Xc * Xc * w[:, None]).sum(0))
+        Xs = Xc / xs
+        wX = w[:, None] * Xs
+        z = (wX * Xs).sum(0)
+        for c in range(C):
+            ym = (Y_all[r, :, c] * w).sum()
+            resid = Y_all[r, :, c] - ym
+            var = (w * resid * resid).sum()
+            beta = np.zeros(len(act))
+            for _ in range(int(max_iter)):
+                sweeps[r, c] += 1
+                max_delta = 0.0
+                for j in range(len(act)):
+                    bj = beta[j]
+                    rho = (wX[:, j] * (resid + Xs[:, j] * bj)).sum()
+                    bnew = np.sign(rho) * max(abs(rho) - alpha, 0.0) / z[j]
+                    if bnew != bj:
+                        resid = resid + Xs[:, j] * (bj - bnew)
+                        beta[j] = bnew
+                        max_delta = max(max_delta, abs(bnew - bj))
+                if max_delta < tol:
+                    break
+            coef[r, c, act] = beta / xs
+            intercept[r, c] = ym - (coef[r, c] * xm).sum()
+            r2[r, c] = 1.0 - (w * resid * resid).sum() / max(var, 1e-12)
+    return (torch.from_numpy(coef), torch.from_numpy(intercept),
+            torch.from_numpy(r2), torch.from_numpy(sweeps))
+
+
 # -------------------------------------------------------- isolation forest
 # The definition of the fused isolation-forest build; ops/hip/
 # iforest_kernels.hip reproduces it bit for bit.

@@ -133,6 +133,12 @@ int launch_iforest_build(const float*, long, int, int, int, int, int,
 int launch_iforest_compact(const int*, const float*, const int*, const int*,
                            const int*, const int*, const long*, int, int,
                            int*, float*, int*, int*, int*, int*, hipStream_t);
+int lime_fit_max_features();
+int lime_fit_max_outputs();
+long lime_fit_scratch_doubles(int);
+int launch_lime_fit(const int*, const double*, int, int, int, int, double,
+                    double, int, double, double*, double*, double*, double*,
+                    int*, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -1446,6 +1452,55 @@ std::vector<torch::Tensor> iforest_build(torch::Tensor X, long n_trees,
           offsets};
 }
 
+// ------------------------------------------------------------------ LIME fit
+// lime_fit_kernels.hip: every kernel-weighted lasso surrogate of a chunk in
+// one launch, one block per explained row.  states (R, n, ceil(m / 32)) int32
+// bit rows, scores (R, n, C) float64.  Returns coef (R, C, m), intercept,
+// r2 (R, C) float64 and n_sweeps (R, C) int32.
+std::vector<torch::Tensor> lime_fit(torch::Tensor states, long m,
+                                    torch::Tensor scores, double kernel_width,
+                                    double alpha, long max_iter, double tol) {
+  CHECK_DEV(states); CHECK_CONTIG(states);
+  CHECK_DEV(scores); CHECK_CONTIG(scores);
+  TORCH_CHECK(states.device() == scores.device(),
+              "lime_fit: states and scores must share a GPU");
+  TORCH_CHECK(m >= 1 && m <= lime_fit_max_features(),
+              "lime_fit: m must lie in [1, ", lime_fit_max_features(), "]");
+  TORCH_CHECK(states.dtype() == torch::kInt32 && states.dim() == 3 &&
+              states.size(2) == (m + 31) / 32,
+              "lime_fit: states must be int32 (R, n, ceil(m / 32))");
+  const long R = states.size(0), n = states.size(1);
+  TORCH_CHECK(scores.dtype() == torch::kFloat64 && scores.dim() == 3 &&
+              scores.size(0) == R && scores.size(1) == n,
+              "lime_fit: scores must be float64 (R, n, C)");
+  const long C = scores.size(2);
+  TORCH_CHECK(C >= 1 && C <= lime_fit_max_outputs(),
+              "lime_fit: C must lie in [1, ", lime_fit_max_outputs(), "]");
+  TORCH_CHECK(n >= 1 && n < (1L << 31) && R < (1L << 31),
+              "lime_fit: n must lie in [1, 2^31) and R below 2^31");
+  TORCH_CHECK(kernel_width > 0 && alpha >= 0 && tol == tol &&
+              max_iter >= 0 && max_iter < (1L << 31),
+              "lime_fit: kernel_width > 0, alpha >= 0, max_iter >= 0");
+  const auto f64 = scores.options();
+  auto coef = torch::empty({R, C, m}, f64);
+  auto intercept = torch::empty({R, C}, f64);
+  auto r2 = torch::empty({R, C}, f64);
+  auto sweeps = torch::empty({R, C}, f64.dtype(torch::kInt32));
+  if (R == 0) return {coef, intercept, r2, sweeps};
+  const long per_row = lime_fit_scratch_doubles((int)m);
+  auto scratch = torch::empty({R * per_row}, f64);
+  const int err = launch_lime_fit(
+      states.data_ptr<int>(), scores.data_ptr<double>(), (int)R, (int)n,
+      (int)m, (int)C, kernel_width, alpha, (int)max_iter, tol,
+      per_row ? scratch.data_ptr<double>() : nullptr, coef.data_ptr<double>(),
+      intercept.data_ptr<double>(), r2.data_ptr<double>(),
+      sweeps.data_ptr<int>(), cur_stream());
+  TORCH_CHECK(err == 0, "lime_fit launch failed: ",
+              err < 0 ? "argument out of range"
+                      : hipGetErrorString((hipError_t)err));
+  return {coef, intercept, r2, sweeps};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build", &hist_build, "per-leaf (feature,bin) grad/hess/count histogram");
   m.def("hist_build_fixed_pair", &hist_build_fixed_pair,
@@ -1529,6 +1584,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("iforest_staged", &iforest_staged,
         "1 when a tree's sample of sub_n x nf values is staged in LDS");
   m.attr("IFOREST_MAX_SUB") = iforest_max_sub();
+  m.def("lime_fit", &lime_fit,
+        "kernel-weighted lasso surrogates of a chunk of LIME rows, one launch");
+  m.attr("LIME_FIT_MAX_FEATURES") = lime_fit_max_features();
+  m.attr("LIME_FIT_MAX_OUTPUTS") = lime_fit_max_outputs();
   m.attr("SLIC_MAX_K") = kSlicMaxK;
   m.attr("SLIC_MAX_DIM") = kSlicMaxDim;
   m.attr("ALS_MAX_K") = kAlsMaxK;
