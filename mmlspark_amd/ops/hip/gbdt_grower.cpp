@@ -3,13 +3,16 @@
 // Runs the entire leaf-wise loop in C++ with ONE Python call per tree,
 // organized around two ideas:
 //
-//  * ARENA MODE: the tree's working set (paired bin planes + pre-quantized
-//    (gq,hq) records + original row ids) lives in a per-tree DOUBLE-BUFFERED
+//  * ARENA MODE: the tree's working set (paired bin planes + float2 {g, h}
+//    gradient records + original row ids) lives in a per-tree DOUBLE-BUFFERED
 //    arena.  Every split scatters the parent's segment into the other buffer
 //    (stable left|right), so child histograms read CONTIGUOUS rows — the
 //    sparse row gather that bounded child hist builds (measured 2.3x,
-//    profiles/r01_hist_gather_probe.txt) is gone; the cost is ~124 B/row
-//    of arena payload per split, which HBM3E absorbs.  Live leaves always
+//    profiles/r01_hist_gather_probe.txt) is gone; the cost is ~116 B/row
+//    of arena payload per split (100 features), which HBM3E absorbs.  The
+//    histogram turns a record into the fixed-point (gq, CNT|hq) as it loads
+//    it; MMLSPARK_AMD_GROWER_GH_FLOAT=0 keeps 16-byte pre-quantized records
+//    in the arena instead (~124 B/row), with the same sums.  Live leaves always
 //    own disjoint row ranges, so two in-flight splits never overlap even
 //    across buffers.  When the root row set is every row in order (no
 //    bagging, no GOSS), the root reads its planes straight from the static
@@ -54,15 +57,16 @@
 
 extern "C" {
 void launch_arena_gather(const void*, long, const float*, const float*,
-                         const int*, long, int, double, double, void*, void*,
-                         int*, hipStream_t);
+                         const int*, long, int, double, double, int, void*,
+                         void*, int*, hipStream_t);
 void launch_partition_arena(const void*, const void*, const int*, void*,
                             void*, int*, long, int, long, long, int, int,
-                            const unsigned*, int*, int*, long, int,
+                            const unsigned*, int*, int*, long, int, int,
                             hipStream_t);
-void launch_hist_pair_range(const void*, const void*, long, long, long,
-                            long long*, int, int, int, const int*, int, long,
-                            int, int, int, hipStream_t);
+void launch_hist_pair_range(const void*, const void*, int, double, double,
+                            long, long, long, long long*, int, int, int,
+                            const int*, int, long, int, int, int,
+                            hipStream_t);
 void launch_sibling_scan(const long long*, const long long*, long long*, int,
                          long, int, float, float, float, float, long,
                          const bool*, float*, double, double, hipStream_t);
@@ -111,8 +115,9 @@ int grower_streams_from_env() {
   return (int)v;
 }
 
-// On/off switches of the tree's head and tail (docs/kernels.md); all default
-// to on.  Read once per tree, before any launch.
+// On/off switches of the tree's head and tail and of the arena's float
+// records (docs/kernels.md); all default to on.  Read once per tree, before
+// any launch.
 bool grower_switch(const char* name) {
   const char* e = std::getenv(name);
   if (!e || !*e) return true;
@@ -169,7 +174,10 @@ struct GrowCtx {
   // kRootBuf's planes: the static binned_pair when the root reads it in
   // place (never a scatter destination), else null
   const void* root_pair = nullptr;
-  torch::Tensor ghq[2];    // (n_arena, 2) i64 (gq, CNT|hq)
+  // (n_arena, 2) gradient records: f32 (g, h) if gh_float, else i64
+  // (gq, CNT|hq)
+  torch::Tensor ghq[2];
+  bool gh_float = true;
   torch::Tensor rowid[2];  // (n_arena,) i32 original row ids
   long nf;
   double scale_g, scale_h;
@@ -278,7 +286,8 @@ torch::Tensor build_hist(GrowCtx& ctx, int buf, long lo, long m,
                          const int* nl_dev = nullptr, int side = -1) {
   auto hist = hist_slot(ctx, true);
   launch_hist_pair_range(
-      pair_of(ctx, buf), ctx.ghq[small_buf(buf)].data_ptr(), ctx.n_arena, lo, m,
+      pair_of(ctx, buf), ctx.ghq[small_buf(buf)].data_ptr(), ctx.gh_float,
+      ctx.scale_g, ctx.scale_h, ctx.n_arena, lo, m,
       (long long*)hist.data_ptr<int64_t>(), ctx.n_bins, ctx.npairs,
       ctx.tail_bytes, nl_dev, side, 0, hist_threads(), hist_order(),
       hist_layout(), grower_stream());
@@ -489,7 +498,7 @@ void launch_job(GrowCtx& ctx, LeafCand& leaf) {
       ctx.rowid[small_buf(src)].data_ptr<int>(), ctx.pair[dst].data_ptr(),
       ctx.ghq[dst].data_ptr(), ctx.rowid[dst].data_ptr<int>(), ctx.n_arena,
       ctx.npairs, leaf.lo, m, leaf.feat, leaf.bin, cat_bits,
-      scratch, total, 0, 0, grower_stream());
+      scratch, total, 0, 0, ctx.gh_float, grower_stream());
 
   const double CL = leaf.CL, CR = leaf.C - leaf.CL;
   const bool left_small = CL <= CR;  // by GLOBAL counts: same on all ranks
@@ -562,6 +571,7 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
   const bool root_one_wait = grower_switch("MMLSPARK_AMD_GROWER_ROOT_ONE_WAIT");
   const bool apply_here =
       grower_switch("MMLSPARK_AMD_GROWER_APPLY") && preds_col.has_value();
+  ctx.gh_float = grower_switch("MMLSPARK_AMD_GROWER_GH_FLOAT");
   if (rows_identity)
     TORCH_CHECK(ctx.n_arena == n_full && binned_pair.is_contiguous() &&
                 binned_pair.scalar_type() == torch::kInt64,
@@ -623,11 +633,12 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
   ctx.slab_raw = torch::empty({slots, ctx.npairs * 8, ctx.n_bins, 3}, i64d);
   for (int b = 0; b < 2; ++b) {
     ctx.pair[b] = torch::empty({ctx.npairs, ctx.n_arena}, i64d);
-    ctx.ghq[b] = torch::empty({ctx.n_arena, 2}, i64d);
+    ctx.ghq[b] = torch::empty(
+        {ctx.n_arena, 2}, ctx.gh_float ? i64d.dtype(torch::kFloat32) : i64d);
     ctx.rowid[b] = torch::empty({ctx.n_arena},
                                 rows_root.options().dtype(torch::kInt32));
   }
-  // materialize arena buffer 0: bin pairs + quantized (gq,hq) + row ids for
+  // materialize arena buffer 0: bin pairs + (g, h) records + row ids for
   // the (possibly bagged) root row set; with the root on the static planes
   // no plane is copied (zero planes) and pair[0] is first written by the
   // root's grandchildren
@@ -636,8 +647,9 @@ py::dict grow_tree_native(torch::Tensor binned, torch::Tensor binned_pair,
                       grad.data_ptr<float>(), hess.data_ptr<float>(),
                       rows_root.data_ptr<int>(), ctx.n_arena,
                       root_static ? 0 : ctx.npairs,
-                      ctx.scale_g, ctx.scale_h, ctx.pair[0].data_ptr(),
-                      ctx.ghq[0].data_ptr(), ctx.rowid[0].data_ptr<int>(),
+                      ctx.scale_g, ctx.scale_h, ctx.gh_float,
+                      ctx.pair[0].data_ptr(), ctx.ghq[0].data_ptr(),
+                      ctx.rowid[0].data_ptr<int>(),
                       grower_stream());
 
   std::vector<int> feature_, thr_bin_, left_, right_, leaf_idx_;
@@ -891,9 +903,22 @@ void apply_leaf_values(torch::Tensor preds_col, torch::Tensor leaf_rows,
                            leaf_rows.numel(), grower_stream());
 }
 
+// Both record forms of the arena, for the two bindings below: (n_arena, 2)
+// i64 fixed-point or (n_arena, 2) f32 (g, h).  Returns true for the float form.
+static bool check_records(const torch::Tensor& ghq, long n_arena,
+                          const char* what) {
+  TORCH_CHECK(ghq.is_cuda() && ghq.is_contiguous() &&
+              (ghq.scalar_type() == torch::kInt64 ||
+               ghq.scalar_type() == torch::kFloat32) &&
+              ghq.numel() == 2 * n_arena,
+              what, ": contiguous (n_arena, 2) i64 or f32 device tensor");
+  return ghq.scalar_type() == torch::kFloat32;
+}
+
 // Test/tuning entry for the arena partition: scatters rows [lo, lo+m) of the
 // src arena into dst (stable left|right) and returns the device left count.
-// chunk / plane_groups = 0 take the launcher's own policy.
+// chunk / plane_groups = 0 take the launcher's own policy.  The records are
+// moved as they are, i64 or f32 pairs.
 torch::Tensor partition_arena(torch::Tensor pair_src, torch::Tensor ghq_src,
                               torch::Tensor rowid_src, torch::Tensor pair_dst,
                               torch::Tensor ghq_dst, torch::Tensor rowid_dst,
@@ -906,9 +931,9 @@ torch::Tensor partition_arena(torch::Tensor pair_src, torch::Tensor ghq_src,
               pair_src.scalar_type() == torch::kInt64 &&
               pair_dst.is_contiguous() && pair_dst.sizes() == pair_src.sizes(),
               "pair planes: contiguous (npairs, n_arena) i64");
-  TORCH_CHECK(ghq_src.is_contiguous() && ghq_dst.is_contiguous() &&
-              ghq_src.numel() == 2 * n_arena && ghq_dst.numel() == 2 * n_arena,
-              "ghq: contiguous (n_arena, 2) i64");
+  const bool gh_float = check_records(ghq_src, n_arena, "ghq_src");
+  TORCH_CHECK(check_records(ghq_dst, n_arena, "ghq_dst") == gh_float,
+              "ghq_src and ghq_dst must have the same dtype");
   TORCH_CHECK(rowid_src.is_contiguous() && rowid_dst.is_contiguous() &&
               rowid_src.numel() == n_arena && rowid_dst.numel() == n_arena,
               "rowid: contiguous (n_arena,) i32");
@@ -929,7 +954,7 @@ torch::Tensor partition_arena(torch::Tensor pair_src, torch::Tensor ghq_src,
                          ghq_dst.data_ptr(), rowid_dst.data_ptr<int>(),
                          n_arena, (int)npairs, lo, m, (int)feature, (int)thr,
                          bits, scratch.data_ptr<int>(), total.data_ptr<int>(),
-                         chunk, (int)plane_groups, grower_stream());
+                         chunk, (int)plane_groups, gh_float, grower_stream());
   return total;
 }
 
@@ -940,20 +965,21 @@ torch::Tensor partition_arena(torch::Tensor pair_src, torch::Tensor ghq_src,
 // bin byte of the valid features below n_bins: neither can be checked here
 // without reading the arena back.  chunk = 0, threads = 0, order = -1 and
 // layout = -1 take the environment's setting if there is one and else the
-// launcher's policy.
+// launcher's policy.  ghq is (n_arena, 2) i64 fixed-point records, added as
+// they are, or (n_arena, 2) f32 (g, h), quantised with scale_g / scale_h as
+// the arena gather would have.
 void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
                      torch::Tensor hist, long n_bins, long tail_bytes,
                      c10::optional<torch::Tensor> nl_dev, long side,
-                     long chunk, long threads, long order, long layout) {
+                     long chunk, long threads, long order, long layout,
+                     double scale_g, double scale_h) {
   TORCH_CHECK(pair.is_cuda() && pair.is_contiguous() && pair.dim() == 2 &&
               pair.scalar_type() == torch::kInt64,
               "pair planes: contiguous (npairs, n_arena) i64");
   const long n_arena = pair.size(1);
   const long npairs = pair.size(0);
-  TORCH_CHECK(ghq.is_cuda() && ghq.is_contiguous() &&
-              ghq.scalar_type() == torch::kInt64 &&
-              ghq.numel() == 2 * n_arena,
-              "ghq: contiguous (n_arena, 2) i64");
+  const bool gh_float = check_records(ghq, n_arena, "ghq");
+  TORCH_CHECK(scale_g > 0 && scale_h > 0, "scales must be positive");
   TORCH_CHECK(lo >= 0 && m >= 0 && lo + m <= n_arena, "range out of bounds");
   TORCH_CHECK(n_bins >= 1 && n_bins <= 256, "n_bins must be 1..256");
   TORCH_CHECK(tail_bytes >= 1 && tail_bytes <= 8, "tail_bytes must be 1..8");
@@ -973,7 +999,8 @@ void hist_pair_range(torch::Tensor pair, torch::Tensor ghq, long lo, long m,
                 nl_dev->numel() == 1, "nl_dev: (1,) i32 device");
     nl = nl_dev->data_ptr<int>();
   }
-  launch_hist_pair_range(pair.data_ptr(), ghq.data_ptr(), n_arena, lo, m,
+  launch_hist_pair_range(pair.data_ptr(), ghq.data_ptr(), gh_float, scale_g,
+                         scale_h, n_arena, lo, m,
                          (long long*)hist.data_ptr<int64_t>(), (int)n_bins,
                          (int)npairs, (int)tail_bytes, nl, (int)side, chunk,
                          threads_r, order_r, layout_r, grower_stream());
@@ -1063,7 +1090,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_bins"), py::arg("tail_bytes"),
         py::arg("nl_dev") = py::none(), py::arg("side") = -1,
         py::arg("chunk") = 0, py::arg("threads") = 0, py::arg("order") = -1,
-        py::arg("layout") = -1);
+        py::arg("layout") = -1, py::arg("scale_g") = 1.0,
+        py::arg("scale_h") = 1.0);
   m.def("sibling_scan", &sibling_scan,
         "fused sibling subtract + per-feature split scan (records, big)",
         py::arg("parent"), py::arg("small"), py::arg("small_is_left"),

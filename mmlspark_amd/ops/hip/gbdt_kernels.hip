@@ -20,6 +20,23 @@
 #define WAVE 64
 #define DEV_INLINE __device__ __forceinline__
 
+// The fixed-point gradient record of one row, {gq, CNT|hq}: the only place a
+// record is made.  It is a pure function of two floats and the tree's two
+// scales, so an arena may carry the 8-byte float2 {g, h} instead and every
+// reader still adds the same integers (gh_load).
+DEV_INLINE longlong2 gh_record(float g, float h, double scale_g,
+                               double scale_h) {
+  longlong2 q;
+  q.x = (long long)llrint((double)g * scale_g);
+  q.y = (long long)((1ull << 44)
+                    | (unsigned long long)llrint((double)h * scale_h));
+  return q;
+}
+DEV_INLINE longlong2 gh_load(longlong2 r, double, double) { return r; }
+DEV_INLINE longlong2 gh_load(float2 r, double scale_g, double scale_h) {
+  return gh_record(r.x, r.y, scale_g, scale_h);
+}
+
 // ---------------------------------------------------------------- histogram
 // binned: (ngroups, n_rows) uchar4; rows: (m,) i32 sorted; grad/hess: (n_rows,)
 // hist:   (ngroups*4, n_bins, 3) f32, pre-zeroed.
@@ -107,7 +124,6 @@ __global__ void hist_build_fixed_pair_k(
   const unsigned long long* plane = binned_pair + (size_t)pair * n_rows;
   const long start = (long)blockIdx.x * chunk;
   const long end = min(start + chunk, m);
-  constexpr unsigned long long CNT_ONE = 1ull << 44;
 
   constexpr int ILP = 4;
   long i = start + tid;
@@ -121,9 +137,9 @@ __global__ void hist_build_fixed_pair_k(
     for (int u = 0; u < ILP; ++u) v[u] = plane[r[u]];
 #pragma unroll
     for (int u = 0; u < ILP; ++u) {
-      gq[u] = (long long)llrint((double)grad[r[u]] * scale_g);
-      hq[u] = CNT_ONE
-              | (unsigned long long)llrint((double)hess[r[u]] * scale_h);
+      const longlong2 q = gh_record(grad[r[u]], hess[r[u]], scale_g, scale_h);
+      gq[u] = q.x;
+      hq[u] = (unsigned long long)q.y;
     }
 #pragma unroll
     for (int u = 0; u < ILP; ++u) {
@@ -140,9 +156,9 @@ __global__ void hist_build_fixed_pair_k(
   for (; i < end; i += blockDim.x) {  // tail
     const int r = rows[i];
     const unsigned long long v = plane[r];
-    const long long gq = (long long)llrint((double)grad[r] * scale_g);
-    const unsigned long long hq =
-        CNT_ONE | (unsigned long long)llrint((double)hess[r] * scale_h);
+    const longlong2 q = gh_record(grad[r], hess[r], scale_g, scale_h);
+    const long long gq = q.x;
+    const unsigned long long hq = (unsigned long long)q.y;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (j >= jmax) break;
@@ -329,47 +345,65 @@ __global__ void part_scatter_k(const uchar4* __restrict__ binned, long n_rows,
 
 // ------------------------------------------------------------- arena mode
 // Per-tree physical repartitioning: the tree's working set lives in a
-// double-buffered ARENA of paired bin planes + pre-quantized (gq,hq)
-// records + original row ids.  Every split SCATTERS the parent's segment
-// into the other buffer (left|right, stable), so child histograms read
-// CONTIGUOUS rows — the sparse row gather that bounded child hist builds
+// double-buffered ARENA of paired bin planes + gradient records + original
+// row ids.  Every split SCATTERS the parent's segment into the other buffer
+// (left|right, stable), so child histograms read CONTIGUOUS rows — the
+// sparse row gather that bounded child hist builds
 // (profiles/r01_hist_gather_probe.txt: 2.3x) disappears entirely, at the
-// cost of moving ~124 B/row/split of arena payload (HBM streaming, ~8 TB/s).
+// cost of moving ~116 B/row/split of arena payload at 100 features (13
+// planes x 8 + 8 record + 4 row id; HBM streaming, ~8 TB/s).  The record is
+// the float2 {g, h}, quantised by gh_record where the histogram loads it; the
+// 16-byte fixed-point form (~124 B/row/split) stays for the bindings and for
+// MMLSPARK_AMD_GROWER_GH_FLOAT=0.
 
+// REC is the arena's gradient record: float2 {g, h}, which the histogram
+// quantises on load, or the 16-byte fixed-point record made here.
+template <typename REC>
 __global__ void arena_gather_k(const unsigned long long* __restrict__ pair_src,
                                long n_src, const float* __restrict__ grad,
                                const float* __restrict__ hess,
                                const int* __restrict__ rows, long m,
                                int npairs, double scale_g, double scale_h,
                                unsigned long long* __restrict__ pair_dst,
-                               longlong2* __restrict__ ghq_dst,
+                               REC* __restrict__ ghq_dst,
                                int* __restrict__ rowid_dst) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const int r = rows[i];
   rowid_dst[i] = r;
-  longlong2 q;
-  q.x = (long long)llrint((double)grad[r] * scale_g);
-  q.y = (long long)((1ull << 44)
-                    | (unsigned long long)llrint((double)hess[r] * scale_h));
-  ghq_dst[i] = q;
+  if constexpr (sizeof(REC) == sizeof(float2))
+    ghq_dst[i] = make_float2(grad[r], hess[r]);
+  else
+    ghq_dst[i] = gh_record(grad[r], hess[r], scale_g, scale_h);
   for (int p = 0; p < npairs; ++p)
     pair_dst[(size_t)p * m + i] = pair_src[(size_t)p * n_src + r];
 }
 
+// gh_float: 1 writes float2 {g, h} records (the scales are not used), 0 the
+// 16-byte fixed-point records
 extern "C" void launch_arena_gather(const void* pair_src, long n_src,
                                     const float* grad, const float* hess,
                                     const int* rows, long m, int npairs,
                                     double scale_g, double scale_h,
-                                    void* pair_dst, void* ghq_dst,
-                                    int* rowid_dst, hipStream_t stream) {
+                                    int gh_float, void* pair_dst,
+                                    void* ghq_dst, int* rowid_dst,
+                                    hipStream_t stream) {
   if (m == 0) return;
   const long blocks = (m + 255) / 256;
-  hipLaunchKernelGGL(arena_gather_k, dim3((unsigned)blocks), dim3(256), 0,
-                     stream, (const unsigned long long*)pair_src, n_src, grad,
-                     hess, rows, m, npairs, scale_g, scale_h,
-                     (unsigned long long*)pair_dst, (longlong2*)ghq_dst,
-                     rowid_dst);
+  if (gh_float)
+    hipLaunchKernelGGL(arena_gather_k<float2>, dim3((unsigned)blocks),
+                       dim3(256), 0, stream,
+                       (const unsigned long long*)pair_src, n_src, grad, hess,
+                       rows, m, npairs, scale_g, scale_h,
+                       (unsigned long long*)pair_dst, (float2*)ghq_dst,
+                       rowid_dst);
+  else
+    hipLaunchKernelGGL(arena_gather_k<longlong2>, dim3((unsigned)blocks),
+                       dim3(256), 0, stream,
+                       (const unsigned long long*)pair_src, n_src, grad, hess,
+                       rows, m, npairs, scale_g, scale_h,
+                       (unsigned long long*)pair_dst, (longlong2*)ghq_dst,
+                       rowid_dst);
 }
 
 __global__ void part_arena_count_k(const unsigned long long* __restrict__ pair,
@@ -405,17 +439,20 @@ __global__ void part_arena_count_k(const unsigned long long* __restrict__ pair,
 // Each block derives its own exclusive offset and the left total from the
 // count kernel's block_counts (<= 4096 ints, L2-resident), so no scan kernel
 // sits between count and scatter; the kernel boundary orders the two.
+// SMALL is the gradient record as an opaque element of 8 or 16 bytes: the
+// scatter moves it and never looks inside.
 #define PART_PLANE_BATCH 4
 // launcher policy: rows per block, and the leaf size below which the planes
 // are split into y-groups of PART_PLANE_BATCH — see launch_partition_arena
 #define PART_CHUNK_DEFAULT 1024
 #define PART_SPLIT_PLANES_BELOW (1l << 19)
 
+template <typename SMALL>
 __global__ void part_arena_scatter_k(
     const unsigned long long* __restrict__ pair_src,
-    const longlong2* __restrict__ ghq_src, const int* __restrict__ rowid_src,
+    const SMALL* __restrict__ ghq_src, const int* __restrict__ rowid_src,
     unsigned long long* __restrict__ pair_dst,
-    longlong2* __restrict__ ghq_dst, int* __restrict__ rowid_dst,
+    SMALL* __restrict__ ghq_dst, int* __restrict__ rowid_dst,
     long n_arena, int npairs, int ppg, long lo, long m, int pf, int jbyte,
     int thr, const unsigned* __restrict__ cat_bits, long chunk,
     const int* __restrict__ block_counts, int n_blocks,
@@ -515,10 +552,13 @@ extern "C" void launch_partition_arena(
     void* pair_dst, void* ghq_dst, int* rowid_dst, long n_arena, int npairs,
     long lo, long m, int feature, int thr, const unsigned* cat_bits,
     int* scratch, int* total_left, long chunk_override, int groups_override,
-    hipStream_t stream) {
+    int gh_float, hipStream_t stream) {
   if (m == 0) return;
   // Policy from tools/partition_sweep.py on MI355X (13 planes, count+scatter,
-  // median us; chunk x plane groups):
+  // median us; chunk x plane groups; measured with the 16-byte records, 124
+  // B/row each way.  With float2 records the policy column measured 620 us
+  // at 10^7 rows and 255 at 2^22 against 655 and 270, the same within 1 us
+  // from 2^20 down, profiles/gh_float_partition.txt; not re-swept):
   //   rows     1024x1  1024x4  1024x13  4096x1  4096x13
   //   2^14      21.5    18.8    18.5     43.9    27.7
   //   2^16      23.2    19.1    20.1     44.8    29.0
@@ -549,13 +589,24 @@ extern "C" void launch_partition_arena(
   hipLaunchKernelGGL(part_arena_count_k, dim3((unsigned)blocks), dim3(256),
                      0, stream, (const unsigned long long*)pair_src, n_arena,
                      lo, m, pf, jbyte, thr, cat_bits, chunk, scratch);
-  hipLaunchKernelGGL(part_arena_scatter_k,
-                     dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0,
-                     stream, (const unsigned long long*)pair_src,
-                     (const longlong2*)ghq_src, rowid_src,
-                     (unsigned long long*)pair_dst, (longlong2*)ghq_dst,
-                     rowid_dst, n_arena, npairs, ppg, lo, m, pf, jbyte, thr,
-                     cat_bits, chunk, scratch, (int)blocks, total_left);
+  // gh_float: the records are float2 {g, h}, moved as 8 opaque bytes
+  if (gh_float)
+    hipLaunchKernelGGL(part_arena_scatter_k<unsigned long long>,
+                       dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0,
+                       stream, (const unsigned long long*)pair_src,
+                       (const unsigned long long*)ghq_src, rowid_src,
+                       (unsigned long long*)pair_dst,
+                       (unsigned long long*)ghq_dst, rowid_dst, n_arena,
+                       npairs, ppg, lo, m, pf, jbyte, thr, cat_bits, chunk,
+                       scratch, (int)blocks, total_left);
+  else
+    hipLaunchKernelGGL(part_arena_scatter_k<longlong2>,
+                       dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0,
+                       stream, (const unsigned long long*)pair_src,
+                       (const longlong2*)ghq_src, rowid_src,
+                       (unsigned long long*)pair_dst, (longlong2*)ghq_dst,
+                       rowid_dst, n_arena, npairs, ppg, lo, m, pf, jbyte, thr,
+                       cat_bits, chunk, scratch, (int)blocks, total_left);
 }
 
 // range-mode histogram over arena segments: rows are CONTIGUOUS [lo+base,
@@ -610,36 +661,49 @@ DEV_INLINE void hist_rot_row(unsigned long long* lds, int copy, int rot,
   }
 }
 
-template <int STRIDE, bool FULL>
+template <int STRIDE, bool FULL, typename REC>
 DEV_INLINE void hist_rot_rows(unsigned long long* lds, int tid, int jmax,
                               const unsigned long long* __restrict__ plane,
-                              const longlong2* __restrict__ gh, long start,
-                              long end) {
+                              const REC* __restrict__ gh, double scale_g,
+                              double scale_h, long start, long end) {
   const int copy = STRIDE == 16 ? (tid & 8) : 0;
   const int rot = 8 * (tid & 7);
   constexpr int ILP = 4;
   long i = start + tid;
   for (; i + (ILP - 1) * (long)blockDim.x < end; i += ILP * blockDim.x) {
     unsigned long long v[ILP];
+    REC r[ILP];
     longlong2 q[ILP];
 #pragma unroll
     for (int u = 0; u < ILP; ++u) v[u] = plane[i + u * blockDim.x];
 #pragma unroll
-    for (int u = 0; u < ILP; ++u) q[u] = gh[i + u * blockDim.x];
+    for (int u = 0; u < ILP; ++u) r[u] = gh[i + u * blockDim.x];
+#pragma unroll
+    for (int u = 0; u < ILP; ++u) q[u] = gh_load(r[u], scale_g, scale_h);
 #pragma unroll
     for (int u = 0; u < ILP; ++u)
       hist_rot_row<STRIDE, FULL>(lds, copy, rot, tid, jmax, v[u], q[u]);
   }
   for (; i < end; i += blockDim.x)
-    hist_rot_row<STRIDE, FULL>(lds, copy, rot, tid, jmax, plane[i], gh[i]);
+    hist_rot_row<STRIDE, FULL>(lds, copy, rot, tid, jmax, plane[i],
+                               gh_load(gh[i], scale_g, scale_h));
 }
 
-template <int LAYOUT>
-__global__ void __launch_bounds__(1024) hist_pair_range_k(
-    const unsigned long long* __restrict__ pair, const longlong2* __restrict__ ghq,
-    long n_arena, long lo, long m, long long* __restrict__ hist, int n_bins,
-    int npairs, int tail_bytes, long chunk,
-    const int* __restrict__ nl_dev, int side, int order) {
+//
+// REC is the arena's gradient record (compile-time as well): the fixed-point
+// longlong2, or float2 {g, h}, which gh_load turns into the same longlong2
+// right after the load, with the tree's scales.
+// The float2 forms of layouts 1 and 2 are held to six waves per SIMD (80
+// VGPRs), the occupancy of the longlong2 forms: left alone, the scheduler
+// hoists all four rows' f64 conversions and takes 91.
+template <int LAYOUT, typename REC>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(
+    LAYOUT != 0 && sizeof(REC) == sizeof(float2) ? 6 : 4)))
+hist_pair_range_k(
+    const unsigned long long* __restrict__ pair, const REC* __restrict__ ghq,
+    double scale_g, double scale_h, long n_arena, long lo, long m,
+    long long* __restrict__ hist, int n_bins, int npairs, int tail_bytes,
+    long chunk, const int* __restrict__ nl_dev, int side, int order) {
   long base = 0, m_eff = m;
   if (side >= 0) {
     const long nl = nl_dev[0];
@@ -661,7 +725,7 @@ __global__ void __launch_bounds__(1024) hist_pair_range_k(
   const int jmax = (pair_id == npairs - 1) ? tail_bytes : 8;
   const unsigned long long* plane =
       pair + (size_t)pair_id * n_arena + lo + base;
-  const longlong2* gh = ghq + lo + base;
+  const REC* gh = ghq + lo + base;
   const long start = chunk_id * chunk;
   const long end = min(start + chunk, m_eff);
   long long* out = hist + (size_t)pair_id * 8 * n_bins * 3;
@@ -682,11 +746,14 @@ __global__ void __launch_bounds__(1024) hist_pair_range_k(
     long i = start + tid;
     for (; i + (ILP - 1) * (long)blockDim.x < end; i += ILP * blockDim.x) {
       unsigned long long v[ILP];
+      REC r[ILP];
       longlong2 q[ILP];
 #pragma unroll
       for (int u = 0; u < ILP; ++u) v[u] = plane[i + u * blockDim.x];
 #pragma unroll
-      for (int u = 0; u < ILP; ++u) q[u] = gh[i + u * blockDim.x];
+      for (int u = 0; u < ILP; ++u) r[u] = gh[i + u * blockDim.x];
+#pragma unroll
+      for (int u = 0; u < ILP; ++u) q[u] = gh_load(r[u], scale_g, scale_h);
 #pragma unroll
       for (int u = 0; u < ILP; ++u) {
 #pragma unroll
@@ -701,7 +768,7 @@ __global__ void __launch_bounds__(1024) hist_pair_range_k(
     }
     for (; i < end; i += blockDim.x) {
       const unsigned long long v = plane[i];
-      const longlong2 q = gh[i];
+      const longlong2 q = gh_load(gh[i], scale_g, scale_h);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (j >= jmax) break;
@@ -738,9 +805,11 @@ __global__ void __launch_bounds__(1024) hist_pair_range_k(
       lds64[i < used ? i : HP + i - used] = 0ull;
     __syncthreads();
     if (jmax == 8)
-      hist_rot_rows<STRIDE, true>(lds64, tid, jmax, plane, gh, start, end);
+      hist_rot_rows<STRIDE, true>(lds64, tid, jmax, plane, gh, scale_g,
+                                  scale_h, start, end);
     else
-      hist_rot_rows<STRIDE, false>(lds64, tid, jmax, plane, gh, start, end);
+      hist_rot_rows<STRIDE, false>(lds64, tid, jmax, plane, gh, scale_g,
+                                   scale_h, start, end);
     __syncthreads();
 
     // flush: the same contiguous slots as layout 0, slot k = ((f * n_bins +
@@ -763,16 +832,21 @@ __global__ void __launch_bounds__(1024) hist_pair_range_k(
 
 // threads: 256, 512 or 1024, 0 = policy.  order: 0 or 1, -1 = policy.
 // layout: 0, 1 or 2, -1 = policy.  The caller (gbdt_grower.cpp) has validated
-// all three.
+// all three.  gh_float: ghq holds float2 {g, h} records, quantised with
+// scale_g / scale_h; 0: the 16-byte fixed-point records, scales unused.
 extern "C" void launch_hist_pair_range(
-    const void* pair, const void* ghq, long n_arena, long lo, long m,
-    long long* hist, int n_bins, int npairs, int tail_bytes,
-    const int* nl_dev, int side, long chunk_override, int threads, int order,
-    int layout, hipStream_t stream) {
+    const void* pair, const void* ghq, int gh_float, double scale_g,
+    double scale_h, long n_arena, long lo, long m, long long* hist,
+    int n_bins, int npairs, int tail_bytes, const int* nl_dev, int side,
+    long chunk_override, int threads, int order, int layout,
+    hipStream_t stream) {
   if (m == 0) return;
   // Policy from tools/chain_overlap_probe.py --hist-sweep on MI355X (13
   // planes, kernel alone, median us of 21 alternated repeats; profiles/
-  // hist_bank_sweep.jsonl).  Rows per block, order 0:
+  // hist_bank_sweep.jsonl; measured with the 16-byte records.  With float2
+  // records the policy is 2-7 % slower alone at every size, 471 against 461
+  // us at 10^7 rows, profiles/gh_float_hist_only.jsonl: the quantisation's
+  // f64 work, not bytes; thresholds not re-swept).  Rows per block, order 0:
   //   layout 1, 256 threads
   //   rows     2048   4096   8192  16384  32768  65536
   //   2^14     11.3   13.1   17.0   25.6
@@ -837,13 +911,23 @@ extern "C" void launch_hist_pair_range(
   const size_t lds_bytes =
       (layout == 0 ? (size_t)8 * n_bins * 2 : (size_t)(256 + n_bins) * stride) *
       sizeof(long long);
-  auto kern = layout == 0   ? hist_pair_range_k<0>
-              : layout == 1 ? hist_pair_range_k<1>
-                            : hist_pair_range_k<2>;
-  hipLaunchKernelGGL(kern, grid, dim3((unsigned)threads), lds_bytes, stream,
-                     (const unsigned long long*)pair, (const longlong2*)ghq,
-                     n_arena, lo, m, hist, n_bins, npairs, tail_bytes, chunk,
-                     nl_dev, side, order);
+  if (gh_float) {
+    auto kern = layout == 0   ? hist_pair_range_k<0, float2>
+                : layout == 1 ? hist_pair_range_k<1, float2>
+                              : hist_pair_range_k<2, float2>;
+    hipLaunchKernelGGL(kern, grid, dim3((unsigned)threads), lds_bytes, stream,
+                       (const unsigned long long*)pair, (const float2*)ghq,
+                       scale_g, scale_h, n_arena, lo, m, hist, n_bins, npairs,
+                       tail_bytes, chunk, nl_dev, side, order);
+  } else {
+    auto kern = layout == 0   ? hist_pair_range_k<0, longlong2>
+                : layout == 1 ? hist_pair_range_k<1, longlong2>
+                              : hist_pair_range_k<2, longlong2>;
+    hipLaunchKernelGGL(kern, grid, dim3((unsigned)threads), lds_bytes, stream,
+                       (const unsigned long long*)pair, (const longlong2*)ghq,
+                       scale_g, scale_h, n_arena, lo, m, hist, n_bins, npairs,
+                       tail_bytes, chunk, nl_dev, side, order);
+  }
 }
 
 extern "C" void launch_partition(const void* binned, long n_rows,

@@ -22,6 +22,10 @@ one JSON line per size and combination:
 
   python tools/chain_overlap_probe.py --hist-sweep 262144 10000000
 
+--records float (the default, what the grower's arena holds) gives the arena
+float2 {g, h} records, quantised by the histogram as it loads them; --records
+int64 the 16-byte fixed-point records.
+
 With --trace CSV (a rocprofv3 --kernel-trace `*_kernel_trace.csv` of a
 training run) it measures nothing and instead reports for how long intervals
 of the two kernels overlapped in that run:
@@ -121,6 +125,9 @@ def main():
     ap.add_argument("--sweep-chunks", type=int, nargs="+",
                     default=[4096, 16384, 65536])
     ap.add_argument("--sweep-orders", type=int, nargs="+", default=[0, 1])
+    ap.add_argument("--records", choices=["float", "int64"], default="float",
+                    help="arena gradient records: float2 {g, h} or the "
+                    "16-byte fixed-point form")
     ap.add_argument("--trace", default=None,
                     help="rocprofv3 kernel-trace CSV to analyse instead")
     ap.add_argument("--trees", type=int, default=13,
@@ -142,10 +149,19 @@ def main():
     for p in range(npairs):  # plane by plane: no (npairs, n, 8) i64 temporary
         pair[p] = torch.randint(0, nb, (n, 8), device=dev,
                                 dtype=torch.uint8).view(torch.int64).squeeze(1)
-    ghq = torch.stack([
-        torch.randint(-2**40, 2**40, (n,), device=dev, dtype=torch.int64),
-        torch.randint(0, 2**24, (n,), device=dev, dtype=torch.int64)
-        | (1 << 44)], dim=1).contiguous()
+    if args.records == "float":
+        # scales as TreeGrower.set_scales makes them for max |g| = 1, max h =
+        # 0.25 over n rows
+        ghq = torch.stack([
+            torch.rand(n, device=dev) * 2 - 1,
+            torch.rand(n, device=dev) * 0.25], dim=1).contiguous()
+        scales = dict(scale_g=2.0 ** 61 / n, scale_h=2.0 ** 26)
+    else:
+        ghq = torch.stack([
+            torch.randint(-2**40, 2**40, (n,), device=dev, dtype=torch.int64),
+            torch.randint(0, 2**24, (n,), device=dev, dtype=torch.int64)
+            | (1 << 44)], dim=1).contiguous()
+        scales = {}
     rowid = torch.arange(n, device=dev, dtype=torch.int32)
     dst = (torch.empty_like(pair), torch.empty_like(ghq),
            torch.empty_like(rowid))
@@ -157,7 +173,7 @@ def main():
                  order=args.order, layout=args.layout[0]):
         _hip_grower.hist_pair_range(pair, ghq, 0, m, hist, nb, tail,
                                     chunk=chunk, threads=threads, order=order,
-                                    layout=layout)
+                                    layout=layout, **scales)
 
     def run_part(m):
         # threshold at the middle bin of feature 17: about half go left
@@ -203,7 +219,8 @@ def main():
                     ts[lay].append(
                         timed(lambda: run_hist(m, layout=lay)) * 1e3)
             for lay, v in ts.items():
-                print(json.dumps({"m": m, "threads": args.threads,
+                print(json.dumps({"m": m, "records": args.records,
+                                  "threads": args.threads,
                                   "chunk": args.chunk, "order": args.order,
                                   "layout": lay,
                                   "hist_alone_us": pct(v, 0.5),
@@ -227,7 +244,8 @@ def main():
                     ts[cfg].append(timed(lambda: run_hist(m, *cfg)) * 1e3)
             for (t, c, o, lay), v in ts.items():
                 print(json.dumps({
-                    "m": m, "threads": t, "chunk": c, "order": o,
+                    "m": m, "records": args.records, "threads": t,
+                    "chunk": c, "order": o,
                     "layout": lay,
                     "hist_alone_us": round(pct(v, 0.5), 1),
                     "p10": round(pct(v, 0.1), 1),
@@ -251,7 +269,7 @@ def main():
         for _ in range(args.iters):  # alternate the variants in every repeat
             for k, fn in variants.items():
                 ts[k].append(timed(fn) * 1e3)
-        out = {"m": m}
+        out = {"m": m, "records": args.records}
         for k, v in ts.items():
             out[k + "_us"] = round(pct(v, 0.5), 1)
             out[k + "_p10_p90"] = [round(pct(v, 0.1), 1),

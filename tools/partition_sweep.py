@@ -2,8 +2,9 @@
 """Sweep the arena partition's launch policy (rows per block x plane groups)
 over leaf sizes, to set PART_CHUNK_DEFAULT / PART_SPLIT_PLANES_BELOW in
 ops/hip/gbdt_kernels.hip.  Prints one line per (m, chunk, groups): median
-microseconds of count + scatter and the achieved payload rate at 256 B per
-row moved (124 B read + 124 B written + the split plane read by the count).
+microseconds of count + scatter and the achieved payload rate at 240 B per
+row moved with float records (116 B read + 116 B written + the split plane
+read by the count; 13 planes), 256 B with --records int64.
 
   python tools/partition_sweep.py [--npairs 13] [--n-arena 10000000]
 """
@@ -27,6 +28,9 @@ def main():
     ap.add_argument("--groups", type=int, nargs="+", default=None,
                     help="plane-group counts (default 1 2 4 npairs)")
     ap.add_argument("--sizes", type=int, nargs="+", default=None)
+    ap.add_argument("--records", choices=["float", "int64"], default="float",
+                    help="arena gradient records: float2 {g, h} (what the "
+                    "grower's arena holds) or the 16-byte fixed-point form")
     args = ap.parse_args()
     from mmlspark_amd.ops import _hip_grower
     assert torch.cuda.is_available(), "needs a GPU"
@@ -34,12 +38,16 @@ def main():
     n, npairs = args.n_arena, args.npairs
     torch.manual_seed(0)
     src = (torch.randint(0, 2**62, (npairs, n), device=dev, dtype=torch.int64),
-           torch.randint(0, 2**40, (n, 2), device=dev, dtype=torch.int64),
+           (torch.rand(n, 2, device=dev) if args.records == "float" else
+            torch.randint(0, 2**40, (n, 2), device=dev, dtype=torch.int64)),
            torch.arange(n, device=dev, dtype=torch.int32))
     dst = tuple(torch.empty_like(t) for t in src)
     sizes = args.sizes or [1 << 14, 1 << 16, 1 << 18, 1 << 20, 1 << 22, n]
     chunks = args.chunks
     groups = args.groups or sorted({1, 2, 4, npairs})
+    # planes + record + row id, read and written, + the count's split plane
+    row_bytes = 2 * (npairs * 8 + (8 if args.records == "float" else 16) + 4) \
+        + 8
     for m in sizes:
         m = min(m, n)
         best = None
@@ -60,7 +68,7 @@ def main():
                     e1.synchronize()
                     ts.append(e0.elapsed_time(e1) * 1e3)
                 us = sorted(ts)[len(ts) // 2]
-                tbs = m * 256 / (us * 1e-6) / 1e12
+                tbs = m * row_bytes / (us * 1e-6) / 1e12
                 tag = "policy" if chunk == 0 else f"chunk={chunk} groups={g}"
                 print(f"m={m:>9} {tag:<24} {us:9.1f} us  {tbs:5.2f} TB/s",
                       flush=True)
